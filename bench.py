@@ -8,11 +8,14 @@ instance refinement (cosine-similarity head) -> losses -> backward -> fused SGD 
 (reference: wsovod/engine/trainer.py:37-84).  Inputs are resident in HBM before the timed region.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --gpus 1 --steps K --warmup W --full   (+ roofline pass, oracle comparisons, side lines, CPU baseline)
+  python bench.py ... --dump-outputs DIR                  (+ the last timed step's outputs as DIR/<name>.npy)
 
 Prints ONE JSON line on rank 0.  `value` = images/sec over all N GPUs (weak scaling: per-GPU batch fixed).
+A plain run (no --full) does only what that headline needs: set-up, warm-up, the K timed steps, the line.
 The default precision is "parity_mx" (round 6) -- the "parity" mode, which meets the north star's bound (MIL-head logits
 within 1e-3 of the reference path, proposal indexing bit-exact), with its big forward contractions (res4 / res5 convs, fc1 /
-fc2) on the block-scaled f16mx kernels: at N = 1 the line carries that comparison, made with the oracle on the timed batch
+fc2) on the block-scaled f16mx kernels: at N = 1 --full the line carries that comparison, made with the oracle on the timed batch
 itself (the oracle is the checker here, never the thing measured), `roofline.frac` counts ALGORITHMIC flops (the executed
 matrix-pipe work travels as `executed_frac`), and "parity" (bf16x2 everywhere) and plain bf16 are `side` lines.
 """
@@ -100,7 +103,19 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline pass (hipEvent kernel table), the per-precision and "
+                         "at-batch comparisons with the oracle, the side lines and the CPU baseline (each still switched "
+                         "off by its --no-* flag).  Without it a run sets up, warms up, times --steps steps and prints the "
+                         "headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy "
+                         "(float32): the step's losses and, after the deferred update, a fixed seeded sample of every "
+                         "trained tensor (--eval: the detections of the last timed call)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_side = args.no_parity = args.no_cpu_baseline = args.no_roofline = True
+    return args
 
 
 def pmc_traffic(kernel_name, args):
@@ -161,6 +176,48 @@ def to_device_batch(batch, dev):
         if "dataset_id" in x:
             out[-1]["dataset_id"] = x["dataset_id"]
     return out
+
+
+DUMP_SAMPLE = 1 << 16  # --dump-outputs: elements kept of each trained tensor
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes written at most
+
+
+def step_outputs(model, losses):
+    """--dump-outputs of a training step: its losses and the trained tensors after its update, each tensor larger than
+    DUMP_SAMPLE elements as a sample at fixed indices (seeded by the tensor's name: the same elements in every run)."""
+    import zlib
+
+    out = {k: torch.tensor([float(v)], dtype=torch.float32) for k, v in sorted(losses.items())}  # (keys: loss_*)
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        out[f"param.{name}"] = flat.float().cpu()
+    return out
+
+
+def detection_outputs(results):
+    """--dump-outputs of an inference call (--eval): the detections of every image, concatenated in image order."""
+    inst = [r["instances"] for r in results]
+    return {"det_boxes": torch.cat([x.pred_boxes.tensor.float().cpu() for x in inst]),
+            "det_scores": torch.cat([x.scores.float().cpu() for x in inst]),
+            "det_classes": torch.cat([x.pred_classes.float().cpu() for x in inst]),
+            "det_image": torch.cat([torch.full((len(x),), float(i)) for i, x in enumerate(inst)])}
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+
+    total = sum(a.numel() * 4 for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.numpy().astype(np.float32))
 
 
 def cpu_baseline(model, sd, batch, args):
@@ -241,18 +298,22 @@ def eval_bench(args, cfg, model, dev, result_fd):
         out = model.inference(batch, classifier=classifier)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        model.inference(batch, classifier=classifier, do_postprocess=False)
-    torch.cuda.synchronize()
-    elapsed_np = time.perf_counter() - t1
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, detection_outputs(out))
+    elapsed_np = None
+    if args.full:  # side figure: the same calls without the detector post-processing
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            model.inference(batch, classifier=classifier, do_postprocess=False)
+        torch.cuda.synchronize()
+        elapsed_np = time.perf_counter() - t1
     res = {"metric": "inference images/sec (side measurement)", "value": args.batch * args.steps / elapsed,
            "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "dtype": args.precision,
            "data": "synthetic",
            "config": {"workload": f"WSR_{args.depth}_DC5 inference, {args.proposals} proposals/img, {args.classes} classes, "
                                   f"{args.pooler}, score threshold + per-class NMS + top-100 tail", "images_per_step": args.batch,
-                      "ms_per_step_without_detector_postprocess": elapsed_np / args.steps * 1e3,
+                      "ms_per_step_without_detector_postprocess": elapsed_np / args.steps * 1e3 if elapsed_np else None,
                       "detections_first_image": int(len(out[0]["instances"]))}}
     os.write(result_fd, (json.dumps(res) + "\n").encode())
     return 0
@@ -455,9 +516,11 @@ def pick_exchange(trainer, step, sync, dev, algos=("ring", "direct"), warm=2, st
 
 
 def run_config(args, dev, rank, world, *, precision, batch_size, pooler, steps, warmup, h2d=False, rpn=False,
-               want_roofline=False, keep=False, depth=None, proposals=None, classes=None, embed_dim=None, mixed=False):
+               want_roofline=False, keep=False, depth=None, proposals=None, classes=None, embed_dim=None, mixed=False,
+               dump=False):
     """Build the model, run `warmup` + `steps` training steps, return the timing record (and the live objects if keep).
-    mixed: the mixed-dataset model (BASELINE config 5), every step drawn from its largest-vocabulary source."""
+    mixed: the mixed-dataset model (BASELINE config 5), every step drawn from its largest-vocabulary source.
+    dump: the record carries `outputs`, what the last timed step handed its caller (step_outputs)."""
     from wsovod_amd import _lib
     from wsovod_amd.data import make_batch
     from wsovod_amd.engine import HotPathTrainer, build_optimizer
@@ -519,19 +582,22 @@ def run_config(args, dev, rank, world, *, precision, batch_size, pooler, steps, 
     t0 = time.perf_counter()
     events[0].record()
     for i in range(steps):
-        step()
+        last = step()
         events[i + 1].record()
     sync()
     elapsed = time.perf_counter() - t0
     comm = trainer.stats()
     trainer.stats_enable(False)
     per_step = [events[i].elapsed_time(events[i + 1]) for i in range(steps)]
-    last = step()  # outside the timed region: the run must have stayed finite
+    # the last timed step's losses (read before anything else runs: a replayed step graph reuses its output tensors)
     final_losses = {k: float(v.detach()) for k, v in last.items()}
     if not all(v == v and abs(v) != float("inf") for v in final_losses.values()):
         raise RuntimeError(f"training diverged during the benchmark: {final_losses}")
     rec = {"elapsed": elapsed, "per_step_ms": per_step, "final_losses": final_losses, "wire": wire,
            "exchange": trainer.exchange_algo, "exchange_ab": exchange_ab, "comm": comm}
+    if dump:
+        trainer.flush()  # the deferred update of the last timed step: what a caller reads from the parameters after it
+        rec["outputs"] = step_outputs(model, last)
 
     if want_roofline:
         # second pass over the same K steps with every launch bracketed by hipEvents on its stream
@@ -799,7 +865,9 @@ def main():
 
     rec = run_config(args, dev, rank, world, precision=args.precision, batch_size=args.batch, pooler=args.pooler,
                      steps=args.steps, warmup=args.warmup, h2d=args.h2d, rpn=args.rpn,
-                     want_roofline=not args.no_roofline, keep=True)
+                     want_roofline=not args.no_roofline, keep=True, dump=bool(args.dump_outputs) and rank == 0)
+    if "outputs" in rec:
+        write_outputs(args.dump_outputs, rec.pop("outputs"))
     elapsed, my_ms = rec["elapsed"], rec["elapsed"] / args.steps * 1e3
     rank_ms = [my_ms]
     comm_ranks = None
@@ -926,7 +994,6 @@ def main():
                                  "reference's list-of-dicts format as per-image views of ONE collated uint8 batch tensor (the "
                                  "model takes adjacent views as they are: no per-step gather pass; `side` has the H2D form)",
                        "per_step_percentiles": "hipEvent time between consecutive steps on rank 0's stream",
-                       "per_step_ms": [round(v, 3) for v in ms],
                        "rank_ms_per_step": {"max": max(rank_ms), "min": min(rank_ms), "all": rank_ms},
                        "process_group_ranks": dist.get_world_size() if dist.is_initialized() else 1,
                        "process_group": {"backend": dist.get_backend(), "ranks": dist.get_world_size(), "rccl": rccl,
@@ -937,6 +1004,8 @@ def main():
                        "communication": comm_ranks,
                        "final_losses": rec["final_losses"]},
         }
+        if args.full:  # (a plain line stays short whatever --steps is: the percentiles above summarise the list)
+            out["config"]["per_step_ms"] = [round(v, 3) for v in ms]
         if roofline is not None:
             out["roofline"] = roofline
         model, cpu_state, host_batch = rec.pop("model"), rec.pop("cpu_state"), rec.pop("host_batch")

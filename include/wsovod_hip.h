@@ -415,7 +415,8 @@ int wsovod_weighted_l1_box_forward(const float* pred_deltas, long long ldp, cons
  * P = dY, Q = X as the forward pass left them.  ldp, ldq, NI, NJ multiples of 8; operands < 2 GiB.
  * accumulate: bit 0 = add to C; bit 1 = keep a partial last round of 256x256 tiles unsplit.  By default such a round
  * (more than 256 tiles in all, at most 128 in the last round) is cut along the reduction into up to 8 slices per tile
- * that meet by fp32 atomic adds, so that it fills the chip; the summation order of those tiles is then not fixed. */
+ * so that it fills the chip; the slices' partial sums go to a library workspace and a second pass adds them in slice
+ * order, so the result repeats bit for bit. */
 int wsovod_gemm_tn(const void* P, long long ldp, const void* Q, long long ldq, int Mred, int NI, int NJ, float* C,
                    long long ldc, float alpha, int accumulate, wsovod_stream_t stream);
 /* The same with Q in `q_dtype` = WSOVOD_BF16 or WSOVOD_BF16X2 (ldq in values): of a bf16x2 Q only the hi halves are read,

@@ -1133,11 +1133,27 @@ def golden_trainable_stage(r):
     save("g19_freeze_at_4", **arrays)
 
 
+def golden_roi_pool_sizes():
+    """G2b: the reference's compiled RoIPool (oracle/_ref) on a random map and 128 random boxes (edge cases included) at
+    three output sizes -- the vectors the C oracle is held to where the reference's op is not compiled."""
+    from tests.util import random_rois
+
+    feat = torch.randn(3, 5, 40, 50, generator=torch.Generator().manual_seed(76))
+    rois = random_rois(128, 3, 320, 400, seed=77)
+    arrays = dict(feat=feat, rois=rois)
+    for ph, pw in [(7, 7), (3, 5), (1, 1)]:
+        out, arg = roi_ops.ref_roi_pool_forward(feat, rois, 0.125, (ph, pw))
+        arrays[f"out_{ph}x{pw}"], arrays[f"argmax_{ph}x{pw}"] = out, arg
+    save("g2_roi_pool_sizes", **arrays)
+
+
 def main():
     if "--only-sampler" in sys.argv:
         return golden_sampler()
     if "--only-formats" in sys.argv:
         return golden_formats()
+    if "--only-roi-sizes" in sys.argv:
+        return golden_roi_pool_sizes()
     torch.manual_seed(0)
     torch.set_num_threads(8)
     r = load_reference()
@@ -1165,6 +1181,7 @@ def main():
     g = torch.randn(out.shape, generator=torch.Generator().manual_seed(12))
     gi = roi_ops.ref_roi_pool_backward(g, rois, arg, 0.125, feat.shape)
     save("g2_roi_pool", feat=feat, rois=rois, out=out, argmax=arg, grad_out=g, grad_in=gi)
+    golden_roi_pool_sizes()
 
     # ---------------- G1/G3-G9: whole model at the plumbing scale ----------------
     K, D = 20, 512
@@ -1233,7 +1250,8 @@ def main():
     x50 = torch.randn(2, 3, 64, 96, generator=torch.Generator().manual_seed(6))
     with torch.no_grad():
         f50 = model50.backbone(x50)
-    save("g1_backbone_r50_small", x=x50, res5=f50["res5"])
+    save("g1_backbone_r50_small", res5=f50["res5"])  # (input and output in two files: each stays below 1 MiB)
+    save("g1_backbone_r50_small_x", x=x50)
 
     # G5: OV classifier variants on a fixed feature matrix
     feat_x = torch.randn(48, 4096, generator=torch.Generator().manual_seed(21)) * 0.5

@@ -462,9 +462,9 @@ def test_gemm_tn_reduction_longer_than_one_buffer_resource(gpu, monkeypatch):
 
 
 def test_gemm_tn_tail_split_matches_unsplit(gpu):
-    """More than one round of 256x256 tiles with a small last round: the tail tiles are reduced in K slices that meet
-    by atomic adds.  Same result as the unsplit launch up to fp32 summation order; accumulate keeps the old contents;
-    tiles of the full rounds are bit-identical."""
+    """More than one round of 256x256 tiles with a small last round: the tail tiles are reduced in K slices whose partial
+    sums a second pass adds in slice order.  Same result as the unsplit launch up to fp32 summation order; accumulate keeps
+    the old contents; tiles of the full rounds are bit-identical."""
     from wsovod_amd.layers import hip_ops
 
     torch.manual_seed(5)

@@ -301,6 +301,53 @@ def test_subsample_labels_random_keys(gpu):
         assert float((f - p).abs().max()) < 5 * sigma + 1e-9
 
 
+def test_training_step_reductions_are_run_to_run_bit_identical(gpu):
+    """The reductions of the training step that once met by fp32 atomic adds -- the K slices of split weight-gradient
+    tiles (few output tiles: every tile split; a partly filled last round: its tiles split), the bias-gradient column sums
+    of the Linear backward prologue and the two refinement-loss sums -- are written as partials and added in a fixed
+    order: repeated launches on the same inputs give the same bits (and the values of an fp64 reference)."""
+    from wsovod_amd.layers import functions as Fn
+    from wsovod_amd.layers import hip_ops as H
+
+    torch.manual_seed(31)
+    for Mred, NI, NJ in ((16384, 512, 1024), (4096, 256 * 17, 256 * 16)):  # 8 tiles x 8 slices; 272 tiles = 256 + 16 split
+        P = (torch.rand(Mred, NI, device=gpu) - 0.5).to(torch.bfloat16)
+        Q = (torch.rand(Mred, NJ, device=gpu) - 0.5).to(torch.bfloat16)
+        first = H.gemm_tn(P, Q)
+        for _ in range(5):
+            assert torch.equal(H.gemm_tn(P, Q), first)
+        torch.testing.assert_close(first.double(), P.double().t() @ Q.double(), rtol=1e-4, atol=1e-3)
+        acc = torch.randn(NI, NJ, device=gpu)
+        again = H.gemm_tn(P, Q, out=acc.clone(), alpha=0.5, accumulate=True)
+        assert torch.equal(H.gemm_tn(P, Q, out=acc.clone(), alpha=0.5, accumulate=True), again)
+        del P, Q, first, acc, again
+    M, N = 8192, 1024
+    dy = torch.randn(M, N, device=gpu)
+    y = torch.randn(M, N, device=gpu)
+    sums = []
+    for _ in range(5):
+        cs = torch.zeros(N, device=gpu)
+        H.mask_transpose(dy, y, 0.5, torch.bfloat16, want_t=False, colsum=cs)
+        sums.append(cs)
+    assert all(torch.equal(c, sums[0]) for c in sums)
+    want = (dy.double() * (y > 0) * 0.5).sum(0)
+    torch.testing.assert_close(sums[0].double(), want, rtol=1e-5, atol=1e-4)
+    M, K = 16384, 20
+    logits = torch.randn(M, K + 1, device=gpu) * 4
+    gt = torch.randint(-1, K + 1, (M,), device=gpu)
+    w = torch.rand(M, device=gpu)
+    ce = [Fn.weighted_cross_entropy(logits, gt, w, True) for _ in range(5)]
+    assert all(torch.equal(c, ce[0]) for c in ce)
+    pb = torch.rand(M, 4, device=gpu) * 100
+    pb[:, 2:] += pb[:, :2] + 5
+    gb = torch.rand(M, 4, device=gpu) * 100
+    gb[:, 2:] += gb[:, :2] + 5
+    pred = torch.randn(M, 4, device=gpu)
+    wk = torch.where(gt == -1, torch.zeros_like(w), w)
+    l1 = [Fn.weighted_l1_box_loss(pred, pb, gb, gt, wk, K, (10., 10., 5., 5.), 0.0) for _ in range(5)]
+    assert all(torch.equal(v, l1[0]) for v in l1)
+
+
 def test_column_sums_are_run_to_run_bit_identical(gpu):
     """segment_colsum / the NHWC global average pool are fixed-order two-stage reductions (per-chunk fp32 partials, then
     one pass in chunk order): the same input gives the same bits whatever the launch timing, with no quantisation.  (With

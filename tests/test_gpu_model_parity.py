@@ -657,7 +657,7 @@ def test_r50_backbone_matches_reference_golden(gpu, precision, tol):
     from wsovod_amd.modeling.meta_arch import build_backbone
     from wsovod_amd.testing import hot_path_cfg
 
-    g = load_golden("g1_backbone_r50_small")
+    g = dict(load_golden("g1_backbone_r50_small"), **load_golden("g1_backbone_r50_small_x"))
     d = np.load(os.path.join(G, "shapes_r50_backbone.npz"))
     shapes = {str(k)[len("backbone."):]: eval(str(s)) for k, s in zip(d["keys"], d["shapes"])}
     sd = {k[len("backbone."):]: v for k, v in gen.seeded_state({"backbone." + k: s for k, s in shapes.items()}, 3).items()}

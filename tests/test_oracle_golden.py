@@ -32,10 +32,17 @@ def test_roi_pool_c_oracle_matches_reference_op():
     assert torch.equal(gi, g["grad_in"])
 
 
-@pytest.mark.skipif(not roi_ops.ref_available(), reason="oracle/_ref not built and /root/reference absent")
 def test_roi_pool_c_oracle_matches_compiled_reference_random():
+    """Bit for bit against the reference's compiled RoIPool at three output sizes: its stored outputs on a random map
+    (g2_roi_pool_sizes, make_golden.py:golden_roi_pool_sizes) and, where the op is compiled (oracle/_ref), a fresh one."""
     from tests.util import random_rois
 
+    g = load("g2_roi_pool_sizes")
+    for ph, pw in [(7, 7), (3, 5), (1, 1)]:
+        a = roi_ops.roi_pool_forward(g["feat"], g["rois"], 0.125, (ph, pw))
+        assert torch.equal(a[0], g[f"out_{ph}x{pw}"]) and torch.equal(a[1], g[f"argmax_{ph}x{pw}"])
+    if not roi_ops.ref_available():
+        return
     feat = torch.randn(3, 5, 40, 50)
     rois = random_rois(128, 3, 320, 400, seed=77)
     for size in [(7, 7), (3, 5), (1, 1)]:
@@ -163,7 +170,7 @@ def test_rpn_train_step_matches_reference():
 
 
 def test_r50_bottleneck_backbone_matches_reference():
-    g = load("g1_backbone_r50_small")
+    g = dict(load("g1_backbone_r50_small"), **load("g1_backbone_r50_small_x"))
     d = np.load(os.path.join(G, "shapes_r50_backbone.npz"))
     shapes = {str(k): eval(str(s)) for k, s in zip(d["keys"], d["shapes"])}
     sd = gen.seeded_state(shapes, 3)

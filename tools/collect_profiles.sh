@@ -16,9 +16,9 @@ COMMON="--precision $PREC --batch $BATCH"
 SHORT="$COMMON --steps 3 --warmup 2 --no-cpu-baseline --no-roofline --no-side --no-parity"
 FULL=""
 if [ "$PREC" != "parity_mx" ]; then FULL="--no-side --no-parity --no-cpu-baseline"; fi
-python3 "$ROOT/bench.py" $COMMON --steps 20 --warmup 5 $FULL > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+python3 "$ROOT/bench.py" $COMMON --steps 20 --warmup 5 --full $FULL > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
 rm -rf /tmp/prof_kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o kt -- \
-    python3 "$ROOT/bench.py" $COMMON --steps 20 --warmup 5 --no-cpu-baseline --no-side --no-parity > "$OUT/bench_${TAG}_under_rocprof.json" 2> "$OUT/rocprof_$TAG.err"
+    python3 "$ROOT/bench.py" $COMMON --steps 20 --warmup 5 --full --no-cpu-baseline --no-side --no-parity > "$OUT/bench_${TAG}_under_rocprof.json" 2> "$OUT/rocprof_$TAG.err"
 cp /tmp/prof_kt/*kernel_stats.csv "$OUT/kernel_stats_$TAG.csv"
 declare -A PASS
 PASS[FETCH_SIZE]="FETCH_SIZE"

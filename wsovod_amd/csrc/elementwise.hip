@@ -4,6 +4,8 @@
 // All are coalesced 16-B-per-lane streaming kernels; none is reshaped into a GEMM.
 #include "common.h"
 #include "f16mx.h"
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -754,7 +756,7 @@ __global__ __launch_bounds__(256) void mask_transpose_kernel(const TI* __restric
                                                              const TY* __restrict__ y, long long ldy, int M, int N,
                                                              float scale, TO* __restrict__ dA, long long ldda,
                                                              TO* __restrict__ dAt, long long ldt,
-                                                             float* __restrict__ colsum) {
+                                                             float* __restrict__ colsum, float* __restrict__ colpart) {
   __shared__ float tile[64][65];
   const int tid = threadIdx.x;
   const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
@@ -788,7 +790,9 @@ __global__ __launch_bounds__(256) void mask_transpose_kernel(const TI* __restric
     for (int j = 0; j < 8; ++j) tile[row][cg + j] = v[j];
   }
   __syncthreads();
-  if (colsum) {  // bias gradient: column sums of the masked tile (rows past M hold zeros), one atomic per column and tile
+  // bias gradient: column sums of the masked tile (rows past M hold zeros) -- into colpart[tile row][column], which
+  // colsum_rows_kernel adds up in row order (without a workspace: one atomic per column and tile into colsum)
+  if (colsum) {
     __shared__ float part[4][64];
     const int col = tid & 63, q = tid >> 6;
     float sacc = 0.f;
@@ -798,7 +802,8 @@ __global__ __launch_bounds__(256) void mask_transpose_kernel(const TI* __restric
     __syncthreads();
     if (q == 0 && n0 + col < N) {
       const float t = (part[0][col] + part[1][col]) + (part[2][col] + part[3][col]);
-      if (t != 0.f) atomicAdd(colsum + n0 + col, t);
+      if (colpart) colpart[(long long)blockIdx.y * N + n0 + col] = t;
+      else if (t != 0.f) atomicAdd(colsum + n0 + col, t);
     }
   }
   if (dAt) {
@@ -863,6 +868,50 @@ __global__ void scale_rows_kernel(const float* __restrict__ x, long long ldx, co
   }
 }
 
+// colsum[n] += sum over the tile rows t of colpart[t][n] in a fixed order: 32 columns per workgroup, 8 row groups each
+// summing rows g, g + 8, ... in turn, then the 8 group sums added in group order
+__global__ __launch_bounds__(256) void colsum_rows_kernel(const float* __restrict__ colpart, int rows, int N,
+                                                          float* __restrict__ colsum) {
+  __shared__ float part[8][32];
+  const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int n = blockIdx.x * 32 + c;
+  float acc = 0.f;
+  if (n < N) {
+#pragma unroll 4
+    for (int t = g; t < rows; t += 8) acc += colpart[(long long)t * N + n];
+  }
+  part[g][c] = acc;
+  __syncthreads();
+  if (g == 0 && n < N) {
+    float s = part[0][c];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) s += part[q][c];
+    colsum[n] += s;
+  }
+}
+
+// Workspace of the column-sum partials (single-stream use, as the rest of the library): never freed once handed out (a
+// captured HIP graph keeps its pointer), not grown under stream capture -- nullptr then, and the kernel falls back to atomics
+float* colpart_workspace(size_t floats, hipStream_t s) {
+  static float* ws = nullptr;
+  static size_t ws_floats = 0;
+  static std::vector<float*> retired;
+  if (floats > ws_floats) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return nullptr;
+    const size_t want = std::max(floats, 2 * ws_floats);
+    float* fresh = nullptr;
+    if (hipMalloc((void**)&fresh, want * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    if (ws) retired.push_back(ws);
+    ws = fresh;
+    ws_floats = want;
+  }
+  return ws;
+}
+
 }  // namespace
 
 extern "C" {
@@ -877,16 +926,17 @@ static int mask_transpose_impl(const void* dy, long long lddy, const void* y, lo
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(ceil_div(N, 64), ceil_div(M, 64));
   wsovod::ProfScope prof(slot, s, 0.0, (double)M * N * 4.0 * 3);
-#define MT(TI, TO) hipLaunchKernelGGL((mask_transpose_kernel<TI, TO>), grid, dim3(256), 0, s, (const TI*)dy, lddy, (const TI*)y, ldy, M, N, scale, (TO*)dA, ldda, (TO*)dAt, ldt, colsum)
+  float* colpart = colsum ? colpart_workspace((size_t)grid.y * N, s) : nullptr;
+#define MT(TI, TO) hipLaunchKernelGGL((mask_transpose_kernel<TI, TO>), grid, dim3(256), 0, s, (const TI*)dy, lddy, (const TI*)y, ldy, M, N, scale, (TO*)dA, ldda, (TO*)dAt, ldt, colsum, colpart)
   if (y && y_dtype == WSOVOD_BF16X2) {
     WS_CHECK_ARG(in_dtype == WSOVOD_F32 && N % 8 == 0 && ldy % 4 == 0, "wsovod_mask_transpose: a bf16x2 y needs an fp32 dy and N a multiple of 8");
-#define MTX(TO) hipLaunchKernelGGL((mask_transpose_kernel<float, TO, bf16_t, true>), grid, dim3(256), 0, s, (const float*)dy, lddy, (const bf16_t*)y, ldy, M, N, scale, (TO*)dA, ldda, (TO*)dAt, ldt, colsum)
+#define MTX(TO) hipLaunchKernelGGL((mask_transpose_kernel<float, TO, bf16_t, true>), grid, dim3(256), 0, s, (const float*)dy, lddy, (const bf16_t*)y, ldy, M, N, scale, (TO*)dA, ldda, (TO*)dAt, ldt, colsum, colpart)
     if (out_dtype == WSOVOD_F32) MTX(float);
     else if (out_dtype == WSOVOD_BF16) MTX(bf16_t);
     else { wsovod::set_error("wsovod_mask_transpose: bad dtype"); return WSOVOD_ERR_INVALID_ARGUMENT; }
 #undef MTX
   } else if (y && y_dtype == WSOVOD_BF16 && in_dtype == WSOVOD_F32) {  // (round 6: the plain bf16 rounding of an f16mx output)
-#define MTB(TO) hipLaunchKernelGGL((mask_transpose_kernel<float, TO, bf16_t, false>), grid, dim3(256), 0, s, (const float*)dy, lddy, (const bf16_t*)y, ldy, M, N, scale, (TO*)dA, ldda, (TO*)dAt, ldt, colsum)
+#define MTB(TO) hipLaunchKernelGGL((mask_transpose_kernel<float, TO, bf16_t, false>), grid, dim3(256), 0, s, (const float*)dy, lddy, (const bf16_t*)y, ldy, M, N, scale, (TO*)dA, ldda, (TO*)dAt, ldt, colsum, colpart)
     if (out_dtype == WSOVOD_F32) MTB(float);
     else if (out_dtype == WSOVOD_BF16) MTB(bf16_t);
     else { wsovod::set_error("wsovod_mask_transpose: bad dtype"); return WSOVOD_ERR_INVALID_ARGUMENT; }
@@ -900,6 +950,7 @@ static int mask_transpose_impl(const void* dy, long long lddy, const void* y, lo
   else if (in_dtype == WSOVOD_BF16 && out_dtype == WSOVOD_F32) MT(bf16_t, float);
   else { wsovod::set_error("wsovod_mask_transpose: bad dtype"); return WSOVOD_ERR_INVALID_ARGUMENT; }
 #undef MT
+  if (colpart) hipLaunchKernelGGL(colsum_rows_kernel, dim3(ceil_div(N, 32)), dim3(256), 0, s, colpart, (int)grid.y, N, colsum);
   WS_CHECK_LAUNCH("wsovod_mask_transpose");
   return WSOVOD_OK;
 }

@@ -38,8 +38,11 @@ struct TnArgs {
   int accumulate;
   int tiles_i, tiles_j, group_m;
   // split-K of the LAST, partial round of tiles: blocks [0, full_tiles) own a whole tile; after them every remaining tile
-  // is cut into `ksplit` slices of `slice_steps` K-steps whose partial sums meet by fp32 atomic adds (0 = no split)
+  // is cut into `ksplit` slices of `slice_steps` K-steps (0 = no split).  The plain form writes each slice's partial sums
+  // to `partial` ([tile - full_tiles][slice][256][256] fp32) and tn_sum_slices_kernel adds them into C in slice order:
+  // the result does not depend on the order in which the slices finish
   int full_tiles, ksplit, slice_steps;
+  float* partial;
 #if defined(TN_STAMPS)
   float* dbg;  // instrumented builds only (tools/tn_phases.py): per-group cycle sums of the phase sections
 #endif
@@ -424,14 +427,18 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const TnArgs p) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       const int rbase = i0 + wr * 128 + half * 64;
-      // (TAILBUF: the tile's own 256 x 256 block of the compact scratch instead of its place in C)
-      float* dst = TAILBUF ? p.tail_buf + (long long)(wg - p.full_tiles) * 65536 + (long long)(wr * 128 + half * 64) * 256 + wc * 64
-                           : p.C + (long long)rbase * p.ldc + cbase;
-      const long long ldd = TAILBUF ? 256 : p.ldc;
+      // (TAILBUF: the tile's own 256 x 256 block of the compact scratch instead of its place in C; the plain form: the
+      // slice's own 256 x 256 block of `partial`, written with plain stores)
+      const long long blk = (long long)(wr * 128 + half * 64) * 256 + wc * 64;
+      float* dst = TAILBUF ? p.tail_buf + (long long)(wg - p.full_tiles) * 65536 + blk
+                           : p.partial + ((long long)(wg - p.full_tiles) * p.ksplit + slice) * 65536 + blk;
       for (int row = 0; row < 64; ++row) {
         if (rbase + row >= p.NI) break;
         const float v = stg[row * SROW + ((((lane >> 2) ^ (row & 15)) << 2) | (lane & 3))];
-        if (cbase + lane < p.NJ) unsafeAtomicAdd(dst + row * ldd + lane, v);
+        if (cbase + lane < p.NJ) {
+          if constexpr (TAILBUF) unsafeAtomicAdd(dst + row * 256 + lane, v);
+          else dst[row * 256 + lane] = v;
+        }
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -530,10 +537,10 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const TnArgs p) {
 #undef WS_VMCNT
 }
 
-// zero the output tiles [first_tile, tiles_i*tiles_j) (same tile id -> (i, j) map as the main kernel) before their
-// K slices are added into them
-__global__ __launch_bounds__(256) void tn_zero_tail_kernel(const TnArgs p) {
-  // 16 workgroups per tile (16 rows each): one workgroup per 256-KB tile took 17 us for the 32 tail tiles of fc1's dW
+// the split tiles [full_tiles, tiles_i*tiles_j) (same tile id -> (i, j) map as the main kernel): C (+)= the K slices'
+// partial sums in `partial`, added in slice order (slices past the reduction's end were never written and are skipped)
+__global__ __launch_bounds__(256) void tn_sum_slices_kernel(const TnArgs p) {
+  // 16 workgroups per tile (16 rows each)
   const int wg = p.full_tiles + (blockIdx.x >> 4), part = blockIdx.x & 15;
   const int group_size = p.group_m * p.tiles_j;
   const int group_id = wg / group_size;
@@ -541,17 +548,24 @@ __global__ __launch_bounds__(256) void tn_zero_tail_kernel(const TnArgs p) {
   const int gm = min(p.tiles_i - first_i, p.group_m);
   const int in_group = wg - group_id * group_size;
   const int i0 = (first_i + in_group % gm) * 256 + part * 16, j0 = (in_group / gm) * 256;
+  const int nk_all = (p.Mred + 63) / 64;
+  const int nslices = min(p.ksplit, (nk_all + p.slice_steps - 1) / p.slice_steps);
+  const float* src = p.partial + (long long)(wg - p.full_tiles) * p.ksplit * 65536 + (long long)part * 16 * 256;
   const bool vec = (p.ldc & 3) == 0 && ((uintptr_t)p.C & 15) == 0;
   for (int e = threadIdx.x; e < 16 * 64; e += 256) {
-    const int i = i0 + (e >> 6), j = j0 + (e & 63) * 4;
+    const int r = e >> 6, c4 = (e & 63) * 4;
+    const int i = i0 + r, j = j0 + c4;
     if (i >= p.NI) break;
+    if (j >= p.NJ) continue;  // (NJ % 8 == 0: whole quads)
+    f32x4 acc = *(const f32x4*)(src + r * 256 + c4);
+    for (int z = 1; z < nslices; ++z) acc += *(const f32x4*)(src + (long long)z * 65536 + r * 256 + c4);
     float* c = p.C + (long long)i * p.ldc + j;
-    if (vec && j + 3 < p.NJ) {
-      *(f32x4*)c = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+      if (p.accumulate) acc += *(const f32x4*)c;
+      *(f32x4*)c = acc;
     } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (j + r < p.NJ) c[r] = 0.f;
+      for (int q = 0; q < 4; ++q) c[q] = p.accumulate ? c[q] + acc[q] : acc[q];
     }
   }
 }
@@ -714,8 +728,9 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
   wsovod::ProfScope prof(slot, s, flops, bytes);
   // Tail split: with more than one round of tiles on the 256 CUs, a last round that fills less than half of them is cut
   // along K so that it fills the chip (fc1 dW: 1568 tiles = 6 rounds + 32 tiles -> 32 x 8 slices; one round of a 7-round
-  // launch becomes an eighth of a round plus the atomics).  The summation order of those tiles' slices is not fixed;
-  // `accumulate` bit 1 switches the split off for a bit-reproducible result.
+  // launch becomes an eighth of a round plus a pass that adds the slices).  The slices' partial sums go to a workspace and
+  // tn_sum_slices_kernel adds them in slice order, so the result is the same from run to run; `accumulate` bit 1 switches
+  // the split off (the summation order of an unsplit tile).
   const int ntiles = a.tiles_i * a.tiles_j, cus = 256;
   const int tail = ntiles % cus, nk = ceil_div(Mred, 64);
   a.full_tiles = ntiles;
@@ -724,14 +739,13 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
   int grid = ntiles;
   if (!(accumulate & 2) && ntiles <= cus / 2 && nk >= 32) {
     // Few output tiles (the 1024 -> 512 projection: 8; the stacked heads: 80): EVERY tile is cut along the reduction so
-    // that the grid fills the chip; the slices meet by the same fp32 atomic adds as a split tail round
+    // that the grid fills the chip; the slices meet in the workspace as those of a split tail round
     const int S = std::min(std::min(8, cus / ntiles), nk / 16);
     if (S >= 2) {
       a.full_tiles = 0;
       a.ksplit = S;
       a.slice_steps = (ceil_div(nk, S) + 1) & ~1;  // even: the kernel walks K-steps in pairs
       grid = ntiles * S;
-      if (!a.accumulate) hipLaunchKernelGGL(tn_zero_tail_kernel, dim3(ntiles * 16), dim3(256), 0, s, a);
     }
   } else if (!(accumulate & 2) && ntiles > cus && tail > 0 && tail <= cus / 2 &&
              !(getenv("WSOVOD_TN_TAIL") && getenv("WSOVOD_TN_TAIL")[0] == '0')) {
@@ -741,8 +755,29 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
       a.ksplit = S;
       a.slice_steps = (ceil_div(nk, S) + 1) & ~1;
       grid = a.full_tiles + tail * S;
-      if (!a.accumulate) hipLaunchKernelGGL(tn_zero_tail_kernel, dim3(tail * 16), dim3(256), 0, s, a);
     }
+  }
+  a.partial = nullptr;
+  if (a.ksplit && !upd) {
+    // Workspace of this process (single-stream use, as the rest of the library; the pattern of gemm8.hip's split-K): its
+    // largest possible size (at most 256 slices x 256 KB = 64 MB: split tiles x slices never exceed the 256 CUs) is
+    // allocated at the first split launch and never freed -- a captured HIP graph keeps the pointer it was captured
+    // with -- so it never has to grow.  A first split launch under stream capture is refused, as gemm8's split-K does.
+    static float* ws = nullptr;
+    if (!ws) {
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+        wsovod::set_error("wsovod_gemm_tn: the split-K workspace is allocated at the first split launch, not under stream "
+                          "capture; run a split shape once outside the capture first");
+        return WSOVOD_ERR_UNSUPPORTED;
+      }
+      if (hipMalloc((void**)&ws, (size_t)cus * 65536 * sizeof(float)) != hipSuccess) {
+        ws = nullptr;
+        wsovod::set_error("wsovod_gemm_tn: cannot allocate the split-K workspace");
+        return WSOVOD_ERR_HIP;
+      }
+    }
+    a.partial = ws;
   }
   static const int lean = getenv("WSOVOD_TN_LEAN") ? atoi(getenv("WSOVOD_TN_LEAN")) : 2;
   if (upd) {
@@ -794,6 +829,7 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
     hipLaunchKernelGGL(gemm_tn8_kernel<1>, dim3(grid), dim3(512), lds_bytes, s, a);
   else
     hipLaunchKernelGGL(gemm_tn8_kernel<0>, dim3(grid), dim3(512), lds_bytes, s, a);
+  if (a.partial) hipLaunchKernelGGL(tn_sum_slices_kernel, dim3((ntiles - a.full_tiles) * 16), dim3(256), 0, s, a);
   WS_CHECK_LAUNCH("wsovod_gemm_tn");
   return WSOVOD_OK;
 }

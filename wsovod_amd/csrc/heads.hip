@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void weighted_ce_kernel(const float* __restric
                                                           int K1, const long long* __restrict__ gt,
                                                           const float* __restrict__ w, int weighted,
                                                           float* __restrict__ dlogits, long long ldd,
-                                                          float* __restrict__ accum) {
+                                                          float* __restrict__ accum, float* __restrict__ part) {
   __shared__ float sh_sum[4], sh_cnt[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float lsum = 0.f, lcnt = 0.f;
@@ -206,13 +206,24 @@ __global__ __launch_bounds__(256) void weighted_ce_kernel(const float* __restric
     sh_cnt[wave] = lcnt;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(accum, sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3]);
+  if (threadIdx.x == 0) {  // (part: the block's sum, added up in block order by the finalize; the count is exact either way)
+    const float bs = sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3];
+    if (part) part[blockIdx.x] = bs;
+    else atomicAdd(accum, bs);
     atomicAdd(accum + 1, sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3]);
   }
 }
-__global__ void ce_finalize_kernel(const float* __restrict__ accum, float* __restrict__ loss) {
-  loss[0] = accum[0] / accum[1];
+__global__ void ce_finalize_kernel(float* __restrict__ accum, const float* __restrict__ part, int nparts,
+                                   float* __restrict__ loss) {
+  // (one wavefront: lane l sums parts l, l + 64, ... in turn, then a fixed butterfly over the lanes)
+  float t = 0.f;
+  if (part)
+    for (int b = threadIdx.x; b < nparts; b += 64) t += part[b];
+  t = wave_reduce_sum(t);
+  if (threadIdx.x == 0) {
+    if (part) accum[0] = t;
+    loss[0] = accum[0] / accum[1];
+  }
 }
 
 // ---------------------------------------------------------------------------------
@@ -225,7 +236,8 @@ __global__ void ce_finalize_kernel(const float* __restrict__ accum, float* __res
 __global__ void weighted_l1_kernel(const float* __restrict__ pred, long long ldp, const float* __restrict__ pbox,
                                    const float* __restrict__ gbox, const long long* __restrict__ gt,
                                    const float* __restrict__ w, int M, int K, float wx, float wy, float ww, float wh,
-                                   float beta, int weighted, float* __restrict__ dpred, float* __restrict__ accum) {
+                                   float beta, int weighted, float* __restrict__ dpred, float* __restrict__ accum,
+                                   float* __restrict__ part) {
   float tot = 0.f, bad = 0.f;
   for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
     const long long t = gt[m];
@@ -270,16 +282,23 @@ __global__ void weighted_l1_kernel(const float* __restrict__ pred, long long ldp
   __shared__ float sh[4];
   const float t = block_reduce(tot, sh, false);
   const float b = block_reduce(bad, sh, false);
-  if (threadIdx.x == 0) {
-    if (t != 0.f) atomicAdd(accum, t);
+  if (threadIdx.x == 0) {  // (part: the block's sum, added up in block order by the finalize; the NaN count is exact)
+    if (part) part[blockIdx.x] = t;
+    else if (t != 0.f) atomicAdd(accum, t);
     if (b != 0.f) atomicAdd(accum + 1, b);
   }
 }
-__global__ void l1_finalize_kernel(const float* __restrict__ accum, int M, const int* __restrict__ rows_true,
-                                   float* __restrict__ loss, float* __restrict__ dpred) {
+__global__ void l1_finalize_kernel(const float* __restrict__ accum, const float* __restrict__ part, int nparts, int M,
+                                   const int* __restrict__ rows_true, float* __restrict__ loss, float* __restrict__ dpred) {
   const bool bad = accum[1] > 0.f;
   const float inv = 1.0f / (float)max(rows_true ? *rows_true : M, 1);
-  if (blockIdx.x == 0 && threadIdx.x == 0) loss[0] = bad ? 0.f : accum[0] * inv;
+  if (blockIdx.x == 0 && threadIdx.x < 64) {  // (the first wavefront: the block sums as in ce_finalize_kernel)
+    float t = 0.f;
+    if (part)
+      for (int b = threadIdx.x; b < nparts; b += 64) t += part[b];
+    t = wave_reduce_sum(t);
+    if (threadIdx.x == 0) loss[0] = bad ? 0.f : (part ? t : accum[0]) * inv;
+  }
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)M * 4;
        i += (long long)gridDim.x * blockDim.x)
     dpred[i] = bad ? 0.f : dpred[i] * inv;
@@ -652,6 +671,23 @@ int wsovod_image_bce_backward(const float* dS_img, const int* seg_offsets, int G
   return WSOVOD_OK;
 }
 
+// per-block partial sums of the two loss kernels (at most kLossBlocks blocks each, one slot range per kernel): allocated
+// once, never freed (a captured HIP graph keeps the pointer); nullptr when the first call is under stream capture -- the
+// kernels then add their block sums by atomics
+constexpr int kLossBlocks = 256;
+static float* loss_parts(hipStream_t s) {
+  static float* ws = nullptr;
+  if (!ws) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return nullptr;
+    if (hipMalloc((void**)&ws, 2 * kLossBlocks * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      ws = nullptr;
+    }
+  }
+  return ws;
+}
+
 int wsovod_weighted_ce_forward(const float* logits, long long ld, int M, int K1, const long long* gt_classes,
                                const float* weights, int weighted, float* dlogits, long long ldd, float* accum2,
                                float* loss, wsovod_stream_t stream) {
@@ -660,12 +696,15 @@ int wsovod_weighted_ce_forward(const float* logits, long long ld, int M, int K1,
   hipStream_t s = (hipStream_t)stream;
   wsovod::ProfScope prof(slot, s, 0.0, 0.0);
   (void)hipMemsetAsync(accum2, 0, 2 * sizeof(float), s);
+  float* part = loss_parts(s);
+  int nparts = 0;
   if (M > 0) {
     WS_CHECK_ARG(logits && gt_classes && dlogits && K1 > 0 && (!weighted || weights), "wsovod_weighted_ce_forward: bad argument");
-    hipLaunchKernelGGL(weighted_ce_kernel, dim3(std::min(ceil_div(M, 4), 256)), dim3(256), 0, s, logits, ld, M, K1, gt_classes,
-                       weights, weighted, dlogits, ldd, accum2);
+    nparts = std::min(ceil_div(M, 4), kLossBlocks);
+    hipLaunchKernelGGL(weighted_ce_kernel, dim3(nparts), dim3(256), 0, s, logits, ld, M, K1, gt_classes,
+                       weights, weighted, dlogits, ldd, accum2, part);
   }
-  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(1), 0, s, accum2, loss);
+  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, s, accum2, part, nparts, loss);
   WS_CHECK_LAUNCH("wsovod_weighted_ce_forward");
   return WSOVOD_OK;
 }
@@ -679,15 +718,19 @@ int wsovod_weighted_l1_box_forward(const float* pred_deltas, long long ldp, cons
   hipStream_t s = (hipStream_t)stream;
   wsovod::ProfScope prof(slot, s, 0.0, 0.0);
   (void)hipMemsetAsync(accum2, 0, 2 * sizeof(float), s);
+  float* part = loss_parts(s);
+  float* l1part = part ? part + kLossBlocks : nullptr;
+  int nparts = 0;
   if (M > 0) {
     WS_CHECK_ARG(pred_deltas && proposal_boxes && gt_boxes && gt_classes && dpred && (!weighted || weights),
                  "wsovod_weighted_l1_box_forward: bad argument");
-    hipLaunchKernelGGL(weighted_l1_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, s, pred_deltas, ldp, proposal_boxes,
+    nparts = std::min(ceil_div(M, 256), kLossBlocks);  // (grid-stride loop beyond kLossBlocks x 256 rows)
+    hipLaunchKernelGGL(weighted_l1_kernel, dim3(nparts), dim3(256), 0, s, pred_deltas, ldp, proposal_boxes,
                        gt_boxes, gt_classes, weights, M, K, bbox_weights_host[0], bbox_weights_host[1],
-                       bbox_weights_host[2], bbox_weights_host[3], beta, weighted, dpred, accum2);
+                       bbox_weights_host[2], bbox_weights_host[3], beta, weighted, dpred, accum2, l1part);
   }
-  hipLaunchKernelGGL(l1_finalize_kernel, dim3(std::max(1, ceil_div(M * 4, 256))), dim3(256), 0, s, accum2, M, rows_true, loss,
-                     dpred);
+  hipLaunchKernelGGL(l1_finalize_kernel, dim3(std::max(1, ceil_div(M * 4, 256))), dim3(256), 0, s, accum2, l1part, nparts, M,
+                     rows_true, loss, dpred);
   WS_CHECK_LAUNCH("wsovod_weighted_l1_box_forward");
   return WSOVOD_OK;
 }

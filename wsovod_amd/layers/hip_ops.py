@@ -1323,9 +1323,9 @@ def rpn_label_anchors(anchors, gt_boxes, gt_start, gt_count, thr_lo, thr_hi):
 
 
 GEMM_TN_MAX_OPERAND_BYTES = (1 << 31) - 1  # one buffer resource per operand (tests lower it to exercise the row blocks)
-# WSOVOD_DETERMINISTIC=1: weight-gradient tails / small grids are NOT cut along the reduction (their slices would meet by
-# fp32 atomic adds in no fixed order): every dW is then run-to-run bit-identical, at ~3 % of the step.  The default keeps
-# the split (wsovod_gemm_tn, include/wsovod_hip.h); the bias-gradient and loss sums still meet by a few float atomics.
+# WSOVOD_DETERMINISTIC=1: weight-gradient tails / small grids are NOT cut along the reduction (~3 % of the step): every dW
+# is summed in the order of an unsplit tile.  The default keeps the split (wsovod_gemm_tn, include/wsovod_hip.h), whose
+# slices are added in a fixed order as well: both forms, like the bias-gradient and loss sums, repeat bit for bit.
 DETERMINISTIC = __import__("os").environ.get("WSOVOD_DETERMINISTIC", "0") == "1"
 
 

@@ -262,3 +262,226 @@ def test_optimizer_kernels_refresh_the_f16mx_weight_operand(gpu):
         w.mul_(8.0)
     car2, _ = H.mx_cached(w, tensor_scale=True)
     assert car2 is car and w._mx_scale is byte and int(byte) == int(torch.floor(torch.log2(w.detach().abs().max()))) - 7 + H.MX_WEIGHT_HEADROOM + 127
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The operand range: unit-scale activations from 2^-12 to the top of fp16 (where the q and ql planes saturate), a trained
+# weight grown past its tensor scale's headroom, an activation beyond fp16.
+#
+# What the kernel computes for one product a b (a: unit-scale activation, b: weight with scale 2^s) is
+#     hi_a hi_b + q_a ql_b + ql_a q_b,      hi = fp16(x), lo = x - hi, q = E(x 2^-s) 2^s, ql = E(lo 2^(11-s)) 2^(s-11)
+# with E the OCP e4m3 rounding (to nearest even) clamped to +-448 (mx_sat: the conversion instruction itself does not
+# saturate).  The exact product is a b = hi_a hi_b + a lo_b + lo_a hi_b, hence
+#     kernel - a b = q_a (ql_b - lo_b) + (q_a - a) lo_b + ql_a (q_b - hi_b) + (ql_a - lo_a) hi_b
+# and with e(y) >= |E(y) - y|: min(2^-4 |y| + 2^-10, |y|) for |y| <= 448 (half an ulp of 3 mantissa bits; 2^-10: half the
+# subnormal spacing; never more than |y|, zero is representable), |y| - 448 beyond (the clamp), e_q(x) = 2^s e(x 2^-s), e_ql(x) = 2^(s-11) e(lo 2^(11-s)):
+#     |kernel - a b| <= (|a| + e_q(a)) e_ql(b) + e_q(a) |lo_b| + (|lo_a| + e_ql(a)) (e_q(b) + |lo_b|) + e_ql(a) |hi_b|
+# summed over k.  In range every term is O(2^-15 |a b|); a saturated activation (|a| > 448: |lo_a| up to half an fp16 ulp,
+# ql_a clamped at 448 2^-11) costs at most |lo_a| |hi_b| + |a - 448| |lo_b| ~ 2 2^-11 |a b|: the fp16 product's grade.  The
+# tests hold the kernel to this bound (+ fp32 accumulation), and to the fp64 contraction of its decoded planes -- which pins
+# the clamp: without it a saturated lane converts to NaN.
+# (Out of scope here and noted: a ReLU epilogue (fmaxf) turns a NaN output into 0; the range tests run without ReLU.)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _e4m3_err(y):
+    return torch.where(y > 448.0, y - 448.0, torch.minimum(y * 2.0 ** -4 + 2.0 ** -10, y))
+
+
+def _err_planes(x, s):
+    """|hi|, |lo|, e_q, e_ql of fp32 values x (rows, K) with scale exponents s ((rows, 1) or 0), in fp64."""
+    x = x.double()
+    hi = x.float().half().double()
+    lo = (x - hi).abs()
+    p = torch.exp2(torch.as_tensor(s, dtype=torch.float64, device=x.device))
+    return hi.abs(), lo, p * _e4m3_err(x.abs() / p), p * 2.0 ** -11 * _e4m3_err(lo / (p * 2.0 ** -11))
+
+
+def _bound_terms(a, b, sb):
+    """[(activation plane, weight plane)] whose contractions sum to the bound above."""
+    _, la, qa, lqa = _err_planes(a, 0.0)
+    hb, lb, qb, lqb = _err_planes(b, sb)
+    return [(a.double().abs() + qa, lqb), (qa, lb), (la + lqa, qb + lb), (lqa, hb)]
+
+
+def _ranged(rows, cols, gpu, seed):
+    """Rows whose magnitudes run from 2^-12 to 6e4 (values in [m/2, m], random signs): a quarter of them beyond 448."""
+    g = torch.Generator(device=gpu).manual_seed(seed)
+    m = torch.exp2(torch.linspace(-12.0, float(torch.log2(torch.tensor(6.0e4))), rows, device=gpu)).unsqueeze(1)
+    sign = torch.where(torch.rand(rows, cols, device=gpu, generator=g) < 0.5, -1.0, 1.0)
+    return sign * m * (0.5 + 0.5 * torch.rand(rows, cols, device=gpu, generator=g))
+
+
+def _check_gemm_against_planes_and_product(H, got, a, A, B, sb, b, rows=None):
+    """got (M, N) fp32 from A (unit-scale carrier of a) x B (carrier of b, scales sb): the fp64 planes contraction to fp32
+    accumulation error of the row, the exact product within the derived bound (+ the same accumulation term)."""
+    ha, qa, la = (t.double() for t in H.mx_decode(A))
+    hb, qb, lb = (t.double() for t in H.mx_decode(B, sb))
+    planes = ha @ hb.t() + qa @ lb.t() + la @ qb.t()
+    absprod = a.double().abs() @ b.double().abs().t()
+    acc = 2e-6 * absprod.amax(1, keepdim=True)  # per row: the row's own magnitude
+    bound = sum(x @ w.t() for x, w in _bound_terms(a, b, (sb.double() - 127.0)))
+    err_p = (got.double() - planes).abs()
+    err_x = (got.double() - a.double() @ b.double().t()).abs()
+    if rows is not None:
+        err_p, err_x, acc, bound, absprod = err_p[rows], err_x[rows], acc[rows], bound[rows], absprod[rows]
+    assert bool(torch.isfinite(got if rows is None else got[rows]).all())
+    assert float((err_p - acc).max()) <= 0.0, float((err_p / acc).max())
+    assert float((err_x - bound - acc).max()) <= 0.0, float((err_x / (bound + acc)).max())
+    assert float((bound / absprod).max()) < 2.0 ** -9  # (the bound itself is of the fp16 product's grade)
+    return bound, absprod
+
+
+def test_gemm_with_activations_across_the_fp16_range(gpu):
+    """Unit-scale activations from 2^-12 to 6e4 and 65519 (the largest value fp16 still rounds to 65504): rows beyond 448
+    saturate q, rows beyond ~0.2 / 2^-11 saturate ql.  Against the fp64 contraction of the decoded planes and the exact
+    product within the format's bound (comment above)."""
+    from wsovod_amd.layers import hip_ops as H
+
+    torch.manual_seed(9)
+    M, N, K = 256, 520, 1024
+    a = _ranged(M, K, gpu, 9)
+    a[-1, 5] = 65519.0
+    b = torch.randn(N, K, device=gpu) * 0.05
+    A, _ = H.mx_encode(a, unit=True)
+    B, sb = H.mx_encode(b)
+    _, q, ql = H.mx_decode(A)
+    assert bool((q.abs() == 448).any()) and bool((ql.abs() == 448 * 2.0 ** -11).any())  # both planes saturate somewhere
+    got = H.gemm_mx(A, None, B, sb)
+    bound, absprod = _check_gemm_against_planes_and_product(H, got, a, A, B, sb, b)
+    amax = a.abs().amax(1)
+    small = (amax <= 448 * 2.0 ** -11) & (amax >= 2.0 ** -6)  # (no saturated plane, e4m3-normal: the existing tight bound)
+    assert int(small.sum()) > 20
+    err = (got.double() - a.double() @ b.double().t()).abs()
+    assert float((err[small] / absprod[small]).max()) < 2.0 ** -14
+
+
+def test_residual_and_decode_across_the_fp16_range(gpu):
+    """A unit-scale f16mx tensor stands for hi + ql 2^-11: within |x| 2^-11 of x over the whole fp16 range (ql clamped: the
+    remainder beyond it is at most half an fp16 ulp), in mx_to_f32 and in the kernel's residual epilogue."""
+    from wsovod_amd.layers import hip_ops as H
+
+    M, N, K = 256, 512, 256
+    x = _ranged(M, N, gpu, 10)
+    x[-1, 3] = 65519.0
+    R, _ = H.mx_encode(x, unit=True)
+    dec = H.mx_to_f32(R)
+    assert float(((dec - x).abs() - x.abs() * 2.0 ** -11).max()) <= 0.0
+    torch.manual_seed(10)
+    a = torch.randn(M, K, device=gpu)
+    A, _ = H.mx_encode(a, unit=True)
+    B, sb = H.mx_encode(torch.randn(N, K, device=gpu) * 0.05)
+    plain = H.gemm_mx(A, None, B, sb)
+    got = H.gemm_mx(A, None, B, sb, residual=R, residual_fmt=H.MX)
+    tol = x.abs() * 2.0 ** -11 + 2.0 ** -23 * (plain.abs() + x.abs())  # (+ the rounding of the fp32 addition)
+    assert float(((got - plain - x).abs() - tol).max()) <= 0.0
+
+
+@pytest.mark.parametrize("Cin2", [0, 64])
+def test_conv_with_activations_across_the_fp16_range(gpu, Cin2):
+    """The implicit-GEMM form (3x3, dilation 2, + the fused 1x1 shortcut) on maps whose pixels run from 2^-12 to 6e4: against
+    fp64 convolutions of the decoded planes and the exact convolution within the format's bound (the bound terms convolved)."""
+    import torch.nn.functional as F
+    from wsovod_amd.layers import hip_ops as H
+
+    torch.manual_seed(11)
+    n, Hh, Ww, Cin, Cout, k, dil = 2, 12, 14, 128, 256, 3, 2
+    pad = dil
+    P = n * Hh * Ww
+    perm = torch.randperm(P, device=gpu)  # (magnitudes scattered over the image: every tap sees every range)
+    x = _ranged(P, Cin, gpu, 11)[perm]
+    x[7, 3] = 65519.0
+    X = H.mx_encode(x, unit=True)[0].view(n, Hh, Ww, Cin)
+    w = torch.randn(Cout, k * k * Cin + Cin2, device=gpu) * 0.03
+    W, sw = H.mx_encode(w)
+    X2 = x2 = None
+    if Cin2:
+        x2 = _ranged(P, Cin2, gpu, 12)[torch.randperm(P, device=gpu)]
+        X2 = H.mx_encode(x2, unit=True)[0].view(n, Hh, Ww, Cin2)
+    geom = dict(n_img=n, H=Hh, W=Ww, Cin=Cin, Ho=Hh, Wo=Ww, KH=k, KW=k, stride=1, pad=pad, dil=dil)
+    got = H.gemm_mx(X, None, W, sw, conv=geom, A2=X2).view(P, Cout).double()
+
+    def contract(xp, x2p, wp):  # (P, Cin) / (P, Cin2) activation planes x (Cout, K) weight rows -> (P, Cout), fp64
+        wm = wp[:, :k * k * Cin].double().reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
+        out = F.conv2d(xp.double().view(n, Hh, Ww, Cin).permute(0, 3, 1, 2), wm, None, 1, pad, dil)
+        out = out.permute(0, 2, 3, 1).reshape(P, Cout)
+        if Cin2:
+            out = out + x2p.double() @ wp[:, k * k * Cin:].double().t()
+        return out
+
+    hx, qx, lx = H.mx_decode(X.view(P, Cin))
+    hw, qw, lw = H.mx_decode(W, sw)
+    h2, q2, l2 = H.mx_decode(X2.view(P, Cin2)) if Cin2 else (None, None, None)
+    planes = contract(hx, h2, hw) + contract(qx, q2, lw) + contract(lx, l2, qw)
+    absprod = contract(x.abs(), None if x2 is None else x2.abs(), w.abs())
+    acc = 2e-6 * absprod.amax(1, keepdim=True)
+    s = sw.double() - 127.0
+    terms = _bound_terms(x, w, s)
+    terms2 = _bound_terms(x2, w, s) if Cin2 else [(None, None)] * 4
+    bound = sum(contract(xa, x2a, wa) for (xa, wa), (x2a, _) in zip(terms, terms2))
+    assert bool(torch.isfinite(got).all())
+    assert float(((got - planes).abs() - acc).max()) <= 0.0, float(((got - planes).abs() / acc).max())
+    exact = contract(x, x2, w)
+    assert float(((got - exact).abs() - bound - acc).max()) <= 0.0, float(((got - exact).abs() / (bound + acc)).max())
+    assert float((bound / absprod).max()) < 2.0 ** -9
+
+
+def test_tensor_scale_weight_grown_past_its_headroom(gpu):
+    """A trained weight encoded once with ONE scale (first encode: MX_WEIGHT_HEADROOM binade above its largest magnitude's
+    q range), then grown 8x through the SGD kernel's in-place refresh with the OLD byte: its largest elements saturate q and
+    ql.  The contraction stays within the planes' fp64 contraction and within the derived bound of the exact product; a full
+    re-encode (mx_cached after a change behind the optimizer's back) re-derives the byte and restores the tight bound."""
+    from wsovod_amd.engine.trainer import _mx_shadow, _restamp_shadow
+    from wsovod_amd.layers import hip_ops as H
+
+    torch.manual_seed(13)
+    M, N, K = 256, 512, 1024
+    w = (torch.randn(N, K, device=gpu) * 0.01).requires_grad_(True)
+    w0 = w.detach().clone()
+    car, sc = H.mx_cached(w, tensor_scale=True)
+    byte = w._mx_scale
+    b0 = int(byte)
+    with torch.no_grad():  # w - lr (mu * 0 + g) with g = w, lr = -7: 8 w, the operand refreshed with the byte of the first encode
+        sh = _mx_shadow(w)
+        H.sgd_momentum_multi([(w.data, w.detach().clone(), torch.zeros_like(w0), sh, -7.0, 0.0)], 0.9)
+        torch.autograd.graph.increment_version(w)
+        _restamp_shadow(w, sh)
+    torch.testing.assert_close(w.detach(), 8.0 * w0, rtol=1e-6, atol=0)
+    assert int(byte) == b0 and torch.equal(car.view(torch.int32), H.mx_encode(w.detach(), tensor_byte=byte)[0].view(torch.int32))
+    _, q, ql = H.mx_decode(car, sc)
+    p = 2.0 ** (b0 - 127)
+    assert bool((q.abs() == 448 * p).any()) and bool((ql.abs() == 448 * p * 2.0 ** -11).any())  # saturated
+    a = torch.relu(torch.randn(M, K, device=gpu)) * 3.0
+    A, _ = H.mx_encode(a, unit=True)
+    b = w.detach()
+    got = H.gemm_mx(A, None, car, sc)
+    _, absprod = _check_gemm_against_planes_and_product(H, got, a, A, car, sc, b)
+    with torch.no_grad():
+        w.mul_(1.0)  # a change behind the optimizer's back (a loaded checkpoint): the next use is a full encode
+    car2, sc2 = H.mx_cached(w, tensor_scale=True)
+    assert car2 is car and w._mx_scale is byte and int(byte) == b0 + 3
+    got2 = H.gemm_mx(A, None, car2, sc2)
+    err2 = (got2.double() - a.double() @ b.double().t()).abs()
+    assert float((err2 / absprod).max()) < 2.0 ** -14  # (the re-derived byte restores the in-range bound)
+    _check_gemm_against_planes_and_product(H, got2, a, A, car2, sc2, b)
+
+
+def test_activation_beyond_fp16_makes_its_row_non_finite_only(gpu):
+    """One activation >= 65520 (fp16 rounds it to inf; q saturates, ql is 0 -- no inf - inf) in a row, no ReLU: every output
+    of that row is non-finite, every other row is finite and within the bounds above -- no finite garbage anywhere."""
+    from wsovod_amd.layers import hip_ops as H
+
+    torch.manual_seed(14)
+    M, N, K = 256, 520, 1024
+    a = _ranged(M, K, gpu, 14)
+    r = 100
+    a[r, 17] = 65520.0
+    a[r + 1, 40] = -1.0e5
+    b = torch.randn(N, K, device=gpu) * 0.05
+    A, _ = H.mx_encode(a, unit=True)
+    B, sb = H.mx_encode(b)
+    got = H.gemm_mx(A, None, B, sb)
+    assert not bool(torch.isfinite(got[r]).any()) and not bool(torch.isfinite(got[r + 1]).any())
+    rest = torch.ones(M, dtype=torch.bool, device=gpu)
+    rest[r:r + 2] = False
+    a_rest = a.clone()
+    a_rest[r:r + 2] = 0.0  # (the bound's own planes of the two rows are not evaluated)
+    _check_gemm_against_planes_and_product(H, got, a_rest, A, B, sb, b, rows=rest)

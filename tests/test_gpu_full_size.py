@@ -247,12 +247,13 @@ def test_benchmarked_batch_of_32_images_matches_the_oracle(gpu, precision):
         _assert_parity_mode(rep)
 
 
-def test_config5_wsr50_1024_proposals_1203_classes_matches_the_oracle_at_full_size(gpu):
+def test_config5_wsr50_1024_proposals_1203_classes_matches_the_oracle_at_full_size(gpu, monkeypatch):
     """BASELINE config 5 AT SIZE (reference: meta_arch/rcnn_wsovod_mixed_datasets.py:188-191,237-238): the mixed-dataset
     model on WSR_50 (fc1 100352 -> 4096), one 800x600 image with 1024 proposals from the LVIS-sized source -- its own
     object miner with K = 1203 columns, the (1203, 512) text embeddings handed to the refinement head per call, i.e. the
     region x text GEMM at its only non-trivial size (1024 x 512 x 1204) -- against the oracle, fp32 mode AND the
-    headline precision."""
+    headline precisions ("parity_mx" with its thresholds lowered, as in the bottleneck-stage test above: one image is below
+    them, the f16mx kernels run)."""
     from oracle import compare as OC
     from wsovod_amd.data import make_batch
     from wsovod_amd.testing import build_mixed_model, capture_full_step
@@ -262,7 +263,13 @@ def test_config5_wsr50_1024_proposals_1203_classes_matches_the_oracle_at_full_si
     for x in host:
         x["dataset_id"] = source_id
     want = None
-    for precision in ("fp32", "parity"):
+    for precision in ("fp32", "parity", "parity_mx"):
+        if precision == "parity_mx":
+            from wsovod_amd.modeling.backbone import ResNet
+            from wsovod_amd.modeling.roi_heads import WSOVODROIHeads
+
+            monkeypatch.setattr(ResNet, "MX_MIN_TILES", 1)
+            monkeypatch.setattr(WSOVODROIHeads, "MX_MIN_ROWS", 1)
         cfg, model = build_mixed_model(seed=0, names=("voc_2007_train", "coco_2017_train", "lvis_v1_train"), Ks=Ks, depth=50,
                                        precision=precision, device="cuda:0")
         assert type(model).__name__ == "GeneralizedRCNN_WSOVOD_MixedDatasets"

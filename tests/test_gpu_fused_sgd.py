@@ -92,6 +92,12 @@ def _steps(gpu, monkeypatch, fused, graph, precision, n_steps=6):
     monkeypatch.setenv("WSOVOD_BACKBONE_GRAPH", "0")
     monkeypatch.setenv("WSOVOD_FUSED_SGD", "1" if fused else "0")
     monkeypatch.setenv("WSOVOD_STEP_GRAPH", "1" if graph else "0")
+    if precision == "parity_mx":  # (two small images: below the mode's tile-count thresholds -- lowered, the f16mx kernels run)
+        from wsovod_amd.modeling.backbone import ResNet
+        from wsovod_amd.modeling.roi_heads import WSOVODROIHeads
+
+        monkeypatch.setattr(ResNet, "MX_MIN_TILES", 1)
+        monkeypatch.setattr(WSOVODROIHeads, "MX_MIN_ROWS", 1)
     cfg, model = build_hot_path_model(seed=0, precision=precision, device="cuda:0")
     model.train()
     cfg.SOLVER.BASE_LR = 1e-3
@@ -119,12 +125,16 @@ def _steps(gpu, monkeypatch, fused, graph, precision, n_steps=6):
         xe = getattr(fc1, "_x2_enc", None)
         assert xe is not None and xe[0] == (fc1._version, fc1.data_ptr(), None)
         assert torch.equal(xe[1], H.x2_encode(fc1.detach()))
+    if precision == "parity_mx":  # likewise the f16mx operand (one scale for the tensor, refreshed by the update kernels)
+        me = getattr(fc1, "_mx_enc", None)
+        assert me is not None and me[0] == (fc1._version, fc1.data_ptr(), None) and me[2]
+        assert torch.equal(me[1][0].view(torch.int32), H.mx_encode(fc1.detach(), tensor_byte=fc1._mx_scale)[0].view(torch.int32))
     tr.close()
     assert not hasattr(fc1, "_fused_update")
     return out
 
 
-@pytest.mark.parametrize("precision", ["bf16", "parity"])
+@pytest.mark.parametrize("precision", ["bf16", "parity", "parity_mx"])
 @pytest.mark.parametrize("graph", [False, True])
 def test_trainer_with_fused_fc1_update_equals_the_two_kernel_step(gpu, monkeypatch, precision, graph):
     """HotPathTrainer at 2 images per step, dropout on, six steps under a moving learning rate, eager launches and

@@ -184,6 +184,11 @@ def test_whole_step_graph_reproduces_the_eager_steps(gpu, monkeypatch, precision
             assert [type(g) for g in tr._graphs.values()] == [_StepGraph]  # one layout, one graph, five replays
             assert model.roi_heads.box_head._step == len(batches) and tr.iter == len(batches)
             assert int(model.roi_heads.box_head._step_dev) == 16 * len(batches)
+            if precision == "parity_mx":  # the replays refreshed fc1 / fc2's f16mx operands: their caches stay current
+                from wsovod_amd.engine.trainer import _mx_shadow
+
+                bh = model.roi_heads.box_head
+                assert _mx_shadow(bh.fc1.weight) is not None and _mx_shadow(bh.fc2.weight) is not None
         else:
             assert not tr._graphs
         tr.flush()
@@ -375,6 +380,64 @@ def test_eager_and_replayed_layouts_interleave_in_update_order(gpu, monkeypatch)
             assert abs(e[k] - g[k]) <= 5e-5 * max(abs(e[k]), 1e-3), (s, k, e[k], g[k])
     for k, v in runs["0"][1].items():
         torch.testing.assert_close(runs["1"][1][k], v, rtol=1e-4, atol=1e-5 * float(v.abs().max()) + 1e-9, msg=lambda m: f"{k}: {m}")
+
+
+def test_replays_keep_the_f16mx_weight_cache_current(gpu, monkeypatch):
+    """"parity_mx": fc1 / fc2's f16mx operands are refreshed by the SGD kernels (captured or eager) and their caches re-stamped,
+    so that in steady state no encode pass runs for them -- also when a replayed layout (X) and an eager one (Y, captured at
+    its third sighting) take turns.  A replay leaving the cache stale would cost the next eager step (and the capture of Y's
+    graph) a full encode: amax reduction, scale byte, fc1's 100M elements.  Counted at hip_ops.mx_tensor_scale / mx_encode;
+    at the end the cache is the encoding of the weight as it stands."""
+    from wsovod_amd.engine import HotPathTrainer, build_optimizer
+    from wsovod_amd.engine.trainer import _StepGraph
+    from wsovod_amd.layers import hip_ops as H
+    from wsovod_amd.modeling.backbone import ResNet
+    from wsovod_amd.modeling.roi_heads import WSOVODROIHeads
+    from wsovod_amd.testing import build_hot_path_model
+
+    monkeypatch.setattr(H, "DETERMINISTIC", True)
+    monkeypatch.setenv("WSOVOD_BACKBONE_GRAPH", "0")
+    monkeypatch.setenv("WSOVOD_STEP_GRAPH", "1")
+    monkeypatch.setattr(ResNet, "MX_MIN_TILES", 1)
+    monkeypatch.setattr(WSOVODROIHeads, "MX_MIN_ROWS", 1)
+    X = _varying_batches(6, [(64, 64), (60, 57)], H=256, W=320)
+    Y = _varying_batches(3, [(100, 92)], H=256, W=320)
+    cfg, model = build_hot_path_model(seed=0, precision="parity_mx", device="cuda:0")
+    model.train()
+    cfg.SOLVER.BASE_LR = 1e-3
+    tr = HotPathTrainer(model, build_optimizer(cfg, model))
+    bh = model.roi_heads.box_head
+    fcs = (bh.fc1.weight, bh.fc2.weight)
+    ptrs = {w.data_ptr() for w in fcs}
+    encodes = []
+    scale, encode = H.mx_tensor_scale, H.mx_encode
+
+    def counted_scale(t):
+        if any(t is w for w in fcs):
+            encodes.append("mx_tensor_scale")
+        return scale(t)
+
+    def counted_encode(src, *a, **k):
+        if src.data_ptr() in ptrs:
+            encodes.append("mx_encode")
+        return encode(src, *a, **k)
+
+    monkeypatch.setattr(H, "mx_tensor_scale", counted_scale)
+    monkeypatch.setattr(H, "mx_encode", counted_encode)
+    for b in X[:3]:  # X captured at its third sighting
+        tr.run_step(b)
+    assert [type(g) for g in tr._graphs.values()] == [_StepGraph]
+    encodes.clear()  # (the first use encoded fc1 / fc2 once)
+    for b in [X[3], Y[0], X[4], Y[1], X[5], Y[2]]:  # replay, eager, replay, eager, replay, capture of Y
+        tr.run_step(b)
+    tr.flush()
+    assert len(tr._graphs) == 2
+    assert encodes == [], encodes
+    for w in fcs:
+        me = w._mx_enc
+        assert me[0] == (w._version, w.data_ptr(), None)
+        assert torch.equal(me[1][0].view(torch.int32), encode(w.detach(), tensor_byte=w._mx_scale)[0].view(torch.int32))
+    tr.close()
 
 
 def test_step_graph_cache_is_lru_and_stops_capturing_when_it_thrashes(gpu, monkeypatch):

@@ -976,19 +976,81 @@ def test_backbone_in_image_blocks_equals_the_single_launch(gpu, depth, monkeypat
     """Batches whose NHWC maps pass the 2 GiB one buffer resource addresses (> 139 images of 800x600 at the stem) run
     every conv in image blocks.  With the limit lowered so that 5 small images already need blocks of 2, 2 and 1, the
     res5 map equals the single-launch one bit for bit (images are independent; residual, fused shortcut and fused pool
-    paths included)."""
+    paths included).  A split that is consistent but wrong in both runs is caught against the fp32 model on the same
+    weights."""
+    _image_blocks_equal_the_single_launch(gpu, depth, "bf16", monkeypatch)
+
+
+@pytest.mark.parametrize("precision", ["parity", "parity_mx"])
+@pytest.mark.parametrize("depth", [18, 50])
+def test_backbone_in_image_blocks_equals_the_single_launch_in_the_parity_precisions(gpu, depth, precision, monkeypatch):
+    """The image blocks of the test above in the parity precisions: bf16x2 maps, and "parity_mx" with its thresholds lowered
+    so that res4 / res5 run on the f16mx kernels in both runs (a batch slice does not carry the f16mx tag of the map it was
+    cut from), without the split-K last round (WSOVOD_MX_TAIL=0: the blocked launches have other tile counts, hence another
+    summation order there).  Bit for bit against the single launch, within the north star's bound of the fp32 model."""
+    _image_blocks_equal_the_single_launch(gpu, depth, precision, monkeypatch)
+
+
+def _image_blocks_equal_the_single_launch(gpu, depth, precision, monkeypatch):
+    from wsovod_amd.layers import hip_ops as H
     from wsovod_amd.modeling import backbone as B
     from wsovod_amd.testing import build_hot_path_model
 
+    _lower_mx_thresholds(monkeypatch, precision)
+    monkeypatch.setenv("WSOVOD_MX_TAIL", "0")
+    calls = [0]
+    gemm_mx = H.gemm_mx
+
+    def counted(*a, **k):
+        calls[0] += 1
+        return gemm_mx(*a, **k)
+
+    monkeypatch.setattr(H, "gemm_mx", counted)
     x = torch.randint(0, 256, (5, 3, 96, 128), dtype=torch.uint8)
-    cfg, model = build_hot_path_model(seed=0, depth=depth, precision="bf16", device="cuda:0")
+    cfg, model = build_hot_path_model(seed=0, depth=depth, precision=precision, device="cuda:0")
     inp = [{"image": im} for im in x]
     canvas, sizes_t, sizes = model._canvas(inp)
-    want = model.backbone.forward_uint8(canvas, sizes_t, model._mean, model._std)["res5"]
-    # largest per-image map after conv1: 48 x 64 x 64 channels x 2 bytes
-    monkeypatch.setattr(B, "CONV_MAX_OPERAND_BYTES", 2 * 48 * 64 * 64 * 2 + 1)
-    got = model.backbone.forward_uint8(canvas, sizes_t, model._mean, model._std)["res5"]
+
+    def res5():
+        calls[0] = 0
+        with H.mx_mode(model.mx):
+            out = model.backbone.forward_uint8(canvas, sizes_t, model._mean, model._std)["res5"]
+        assert (calls[0] > 0) == (precision == "parity_mx"), calls[0]  # the f16mx kernels ran (no fall-back to bf16x2)
+        return out
+
+    want = res5()
+    # largest per-image map after conv1: 48 x 64 x 64 channels x 2 bytes (bf16; 4 bytes per value in the parity formats)
+    esize = 2 if precision == "bf16" else 4
+    monkeypatch.setattr(B, "CONV_MAX_OPERAND_BYTES", 2 * 48 * 64 * 64 * esize + 1)
+    got = res5()
     assert got.shape == want.shape and torch.equal(got, want)
+    _, ref_model = build_hot_path_model(seed=0, depth=depth, precision="fp32", device="cuda:0")
+    ref_model.load_state_dict(model.state_dict())
+    ref = ref_model.backbone.forward_uint8(canvas, sizes_t, model._mean, model._std)["res5"].float()
+    tol = 0.12 if precision == "bf16" else 1e-3  # (relative to the map's peak: test_r50_backbone_matches_reference_golden's
+    err = float((got.float() - ref).abs().max()) / float(ref.abs().max())  # bf16 bound; the north star's for parity)
+    assert err < tol, (precision, depth, err)
+
+
+def test_bf16x2_kernels_refuse_f16mx_carriers(gpu):
+    """An f16mx carrier is float32-typed and 4 bytes per value like bf16x2; its format lives on the tensor object only.  The
+    bf16x2 / fp32 GEMM refuses one as A, B, the fused shortcut input or the residual instead of contracting its bytes."""
+    from wsovod_amd.layers import hip_ops as H
+
+    x = torch.randn(64, 64, device=gpu)
+    car, _ = H.mx_encode(x, unit=True)
+    car._mx = True
+    x2 = H.x2_encode(x)
+    view = car.view(64, 64)  # (a whole view carries the tag too)
+    for kw in (dict(A=car, B=x2), dict(A=x2, B=view), dict(A=x2, B=x2, residual=car, residual_x2=True)):
+        with pytest.raises(RuntimeError, match="f16mx"):
+            H.gemm_nt(kw.pop("A"), kw.pop("B"), x2=True, **kw)
+    with pytest.raises(RuntimeError, match="f16mx"):
+        H.gemm_nt(car, x, out_dtype=torch.float32)
+    geom = dict(n_img=1, H=8, W=8, Cin=64, Ho=8, Wo=8, KH=1, KW=1, stride=1, pad=0, dil=1)
+    with pytest.raises(RuntimeError, match="f16mx"):
+        H.gemm_nt(x2.view(1, 8, 8, 64), torch.cat([x2, x2], 1), conv=geom, x2=True, A2=car.view(1, 8, 8, 64))
+    assert H.gemm_nt(x2, x2, x2=True, out_dtype=torch.float32).shape == (64, 64)  # (the untagged carrier is read)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -105,9 +105,24 @@ class _FusedUpdate:
         self.opt = weakref.proxy(optimizer)
         self.param = weakref.ref(param)
         self.max_rows = int(max_rows)
-        self.group = next(g for g in optimizer.param_groups if any(q is param for q in g["params"]))
+        self.group_index = self._find_group(optimizer, param)
         self.calls = 0
         self.armed = False  # only inside the trainer's OWN backward: a caller's loss.backward() on the model gets gradients
+
+    @staticmethod
+    def _find_group(optimizer, param):
+        return next(i for i, g in enumerate(optimizer.param_groups) if any(q is param for q in g["params"]))
+
+    @property
+    def group(self):
+        """The parameter group as it stands NOW: optimizer.load_state_dict replaces the group dicts (a resume), and a
+        scheduler moves the live ones -- a dict kept from construction would hold the hyper-parameters of that time."""
+        groups, p = self.opt.param_groups, self.param()
+        g = groups[self.group_index] if self.group_index < len(groups) else None
+        if g is None or not any(q is p for q in g["params"]):
+            self.group_index = self._find_group(self.opt, p)
+            g = groups[self.group_index]
+        return g
 
     def wants(self, rows):
         p = self.param()
@@ -589,6 +604,14 @@ class HotPathTrainer:
             self._hooks.append(model.register_state_dict_pre_hook(lambda *_a, **_k: self.synchronize()))
         if hasattr(optimizer, "register_state_dict_pre_hook"):
             self._hooks.append(optimizer.register_state_dict_pre_hook(lambda *_a, **_k: self.synchronize()))
+        # a checkpoint loaded into the model or the optimizer (a resume): the pending update lands on the weights it was
+        # computed for first, and the captured step graphs are dropped afterwards -- they hold the addresses of the momentum
+        # buffers optimizer.load_state_dict replaces and of operand copies encoded from the weights before the load
+        for obj in (model, optimizer):
+            if hasattr(obj, "register_load_state_dict_pre_hook"):
+                self._hooks.append(obj.register_load_state_dict_pre_hook(lambda *_a, **_k: self.synchronize()))
+            if hasattr(obj, "register_load_state_dict_post_hook"):
+                self._hooks.append(obj.register_load_state_dict_post_hook(lambda *_a, **_k: self._drop_graphs()))
         if isinstance(optimizer, HipSGD):
             optimizer.grad_scale = 1.0 / self.world
         # model.inference() between steps (EvalHook, TTA wrappers call it directly, past any forward hook) applies the
@@ -624,6 +647,13 @@ class HotPathTrainer:
         self._fused = []
         if getattr(self.model, "_pre_inference", None) is getattr(self, "_pre_inference_hook", None):
             self.model._pre_inference = None
+
+    def _drop_graphs(self):
+        """Forget the captured step graphs (and the backbone's): the next steps of a layout run eagerly or capture anew."""
+        self._graphs.clear()
+        bb = getattr(self.model, "backbone", None)
+        if bb is not None:
+            bb.__dict__.pop("_graphs", None)
 
     def broadcast_parameters(self, src=0):
         if self.exchange:
@@ -1044,11 +1074,14 @@ class HotPathTrainer:
             xe = getattr(p, "_x2_enc", None)
             stamped = sh is not None and sh[1] == p._version
             stamped_x = xe is not None and xe[0] == (p._version, p.data_ptr(), None)
+            stamped_mx = _mx_shadow(p) is not None  # (the f16mx operand the captured SGD launch refreshes)
             torch.autograd.graph.increment_version(p)
             if stamped:
                 p._hip_shadow = (sh[0], p._version)
             if stamped_x:
                 p._x2_enc = ((p._version, p.data_ptr(), None), xe[1])
+            if stamped_mx:
+                p._mx_enc = ((p._version, p.data_ptr(), None), p._mx_enc[1], True)
 
     def run_step(self, data):
         g = self._graph_for(data)

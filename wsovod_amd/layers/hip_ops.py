@@ -248,6 +248,15 @@ def _refuse_undeclared_planar(who, *tensors, declared=False):
                                "(only the first FC layer's forward takes a_planar=True; x2_to_f32 decodes either layout)")
 
 
+def _refuse_mx(who, *tensors):
+    """An f16mx carrier is float32-typed and 4 bytes per value like bf16x2, and its format is recorded on the tensor object
+    only (`mx_of`): a consumer that reads bf16x2 or plain fp32 must refuse it instead of contracting its bytes."""
+    for t in tensors:
+        if t is not None and mx_of(t):
+            raise RuntimeError(f"wsovod_hip {who}: got an f16mx carrier where bf16x2 / fp32 values are read "
+                               "(f16mx operands go to gemm_mx)")
+
+
 def x2_to_f32(x):
     """fp32 values of a bf16x2 tensor in either layout (tests, debugging)."""
     if x2_planar_of(x):
@@ -766,6 +775,7 @@ def gemm_nt(A, B, *, out=None, out_dtype=None, out_t=None, alpha=1.0, row_scale=
     require_gpu(A, B, out, out_t, row_scale, bias, residual, row_group, group_add, mask_src)
     _refuse_undeclared_planar("gemm_nt", A, declared=a_planar)
     _refuse_undeclared_planar("gemm_nt", B, A2)
+    _refuse_mx("gemm_nt", A, B, A2, residual)
     if x2 and (A.dtype != torch.float32 or B.dtype != torch.float32):
         raise RuntimeError("wsovod_hip gemm: bf16x2 operands travel as float32-typed tensors")
     if not x2 and _X3State.active and A.dtype == torch.float32 and B.dtype == torch.float32:

@@ -137,16 +137,28 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
     if H.x3_active() in ("full", "fwd") and x.dtype == torch.float32:
         per_image = max(per_image, Hh * Ww * 3 * Cin * 2)  # the operand the kernel addresses is the [hi | hi | lo] bf16 split
     max_n = max(1, CONV_MAX_OPERAND_BYTES // max(per_image, 1))
+    # the format of the maps is decided once, before any split: f16mx is known only through the tensor object's tag, which a
+    # batch slice (not a whole view) does not carry -- each slice and the concatenated output are tagged again
+    mx = _x2() and H.mx_of(x)
     if N > max_n:
+        def part(t, i, j):
+            sl = t[i:j]
+            if mx and H.mx_of(t):
+                sl._mx = True
+            return sl
+
         parts = []
         for i in range(0, N, max_n):
             j = min(N, i + max_n)
-            parts.append(hip_conv(x[i:j], conv, relu=relu, residual=None if residual is None else residual[i:j],
-                                  pool2=pool2, shortcut=None if shortcut is None else (shortcut[0][i:j], shortcut[1]),
+            parts.append(hip_conv(part(x, i, j), conv, relu=relu, residual=None if residual is None else part(residual, i, j),
+                                  pool2=pool2, shortcut=None if shortcut is None else (part(shortcut[0], i, j), shortcut[1]),
                                   out_fp32=out_fp32))
-        return torch.cat(parts)
+        out = torch.cat(parts)
+        if mx and not out_fp32:
+            out._mx = True
+        return out
     geom = dict(n_img=N, H=Hh, W=Ww, Cin=Cin, Ho=Ho, Wo=Wo, KH=k, KW=k, stride=s, pad=p, dil=d)
-    if _x2() and H.mx_of(x):
+    if mx:
         # "parity_mx": x (and residual / shortcut input) are unit-scale f16mx maps; fp16 hi*hi + block-scaled e4m3 cross terms
         # on the f16mx weights (per-row scales, encoded once: the stages are frozen or re-encoded per optimizer step); the
         # output is f16mx again, or real fp32 for the map that leaves the backbone

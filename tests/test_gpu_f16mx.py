@@ -232,36 +232,35 @@ def test_optimizer_kernels_refresh_the_f16mx_weight_operand(gpu):
     memory): the multi-tensor SGD kernel and the fused weight-gradient + update kernel re-encode it element-wise in their pass
     -- the bytes a fresh encode of the updated parameter with that scale writes -- and the cache is re-stamped (no encode pass
     in steady state)."""
-    from wsovod_amd.engine.trainer import _mx_shadow, _restamp_shadow
     from wsovod_amd.layers import hip_ops as H
+    from wsovod_amd.layers import operand_cache
 
     torch.manual_seed(8)
     NI, NJ, M = 512, 1024, 256
     w = (torch.randn(NI, NJ, device=gpu) * 0.01).requires_grad_(True)
     car, sc = H.mx_cached(w, tensor_scale=True)
-    byte = w._mx_scale
+    byte = operand_cache.scale_byte(w)
     assert int(byte) == int(torch.floor(torch.log2(w.detach().abs().max()))) - 7 + H.MX_WEIGHT_HEADROOM + 127
     assert torch.equal(sc, byte.expand(NI, 1)) and torch.equal(car.view(torch.int32), H.mx_encode(w.detach(), tensor_byte=byte)[0].view(torch.int32))
     hi, q, ql = H.mx_decode(car, sc)
     assert float((hi + ql - w.detach()).abs().max() / w.detach().abs().max()) < 2.0 ** -14
     g, buf = torch.randn(NI, NJ, device=gpu) * 1e-3, torch.zeros(NI, NJ, device=gpu)
-    sh = _mx_shadow(w)
-    assert sh is not None and sh[0] is car
+    fmt, sh = operand_cache.refreshable(w)
+    assert fmt == "mx" and sh[0] is car and sh[1] is byte
     with torch.no_grad():
         H.sgd_momentum_multi([(w.data, g, buf, sh, 0.5, 1e-4)], 0.9)
-        torch.autograd.graph.increment_version(w)
-        _restamp_shadow(w, sh)
+        operand_cache.wrote(w, fmt)
     assert torch.equal(car.view(torch.int32), H.mx_encode(w.detach(), tensor_byte=byte)[0].view(torch.int32))
     assert H.mx_cached(w, tensor_scale=True)[0] is car  # the cache is current: no encode
     dA = (torch.randn(M, NI, device=gpu) * 0.1).to(torch.bfloat16)
     x = torch.randn(M, NJ, device=gpu).to(torch.bfloat16)
     with torch.no_grad():
-        H.gemm_tn_sgd(dA, x, w.data, buf, _mx_shadow(w), 0.01, 1e-4, 0.9)
+        H.gemm_tn_sgd(dA, x, w.data, buf, operand_cache.refreshable(w)[1], 0.01, 1e-4, 0.9)
     assert torch.equal(car.view(torch.int32), H.mx_encode(w.detach(), tensor_byte=byte)[0].view(torch.int32))
     with torch.no_grad():  # a change behind the optimizer's back (a loaded checkpoint): full encode, scale re-derived IN PLACE
         w.mul_(8.0)
     car2, _ = H.mx_cached(w, tensor_scale=True)
-    assert car2 is car and w._mx_scale is byte and int(byte) == int(torch.floor(torch.log2(w.detach().abs().max()))) - 7 + H.MX_WEIGHT_HEADROOM + 127
+    assert car2 is car and operand_cache.scale_byte(w) is byte and int(byte) == int(torch.floor(torch.log2(w.detach().abs().max()))) - 7 + H.MX_WEIGHT_HEADROOM + 127
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -429,21 +428,21 @@ def test_tensor_scale_weight_grown_past_its_headroom(gpu):
     q range), then grown 8x through the SGD kernel's in-place refresh with the OLD byte: its largest elements saturate q and
     ql.  The contraction stays within the planes' fp64 contraction and within the derived bound of the exact product; a full
     re-encode (mx_cached after a change behind the optimizer's back) re-derives the byte and restores the tight bound."""
-    from wsovod_amd.engine.trainer import _mx_shadow, _restamp_shadow
     from wsovod_amd.layers import hip_ops as H
+    from wsovod_amd.layers import operand_cache
 
     torch.manual_seed(13)
     M, N, K = 256, 512, 1024
     w = (torch.randn(N, K, device=gpu) * 0.01).requires_grad_(True)
     w0 = w.detach().clone()
     car, sc = H.mx_cached(w, tensor_scale=True)
-    byte = w._mx_scale
+    byte = operand_cache.scale_byte(w)
     b0 = int(byte)
     with torch.no_grad():  # w - lr (mu * 0 + g) with g = w, lr = -7: 8 w, the operand refreshed with the byte of the first encode
-        sh = _mx_shadow(w)
+        fmt, sh = operand_cache.refreshable(w)
+        assert fmt == "mx"
         H.sgd_momentum_multi([(w.data, w.detach().clone(), torch.zeros_like(w0), sh, -7.0, 0.0)], 0.9)
-        torch.autograd.graph.increment_version(w)
-        _restamp_shadow(w, sh)
+        operand_cache.wrote(w, fmt)
     torch.testing.assert_close(w.detach(), 8.0 * w0, rtol=1e-6, atol=0)
     assert int(byte) == b0 and torch.equal(car.view(torch.int32), H.mx_encode(w.detach(), tensor_byte=byte)[0].view(torch.int32))
     _, q, ql = H.mx_decode(car, sc)
@@ -457,7 +456,7 @@ def test_tensor_scale_weight_grown_past_its_headroom(gpu):
     with torch.no_grad():
         w.mul_(1.0)  # a change behind the optimizer's back (a loaded checkpoint): the next use is a full encode
     car2, sc2 = H.mx_cached(w, tensor_scale=True)
-    assert car2 is car and w._mx_scale is byte and int(byte) == b0 + 3
+    assert car2 is car and operand_cache.scale_byte(w) is byte and int(byte) == b0 + 3
     got2 = H.gemm_mx(A, None, car2, sc2)
     err2 = (got2.double() - a.double() @ b.double().t()).abs()
     assert float((err2 / absprod).max()) < 2.0 ** -14  # (the re-derived byte restores the in-range bound)

@@ -86,6 +86,7 @@ def _steps(gpu, monkeypatch, fused, graph, precision, n_steps=6):
     from wsovod_amd.data import make_batch
     from wsovod_amd.engine import HotPathTrainer, build_optimizer
     from wsovod_amd.layers import hip_ops as H
+    from wsovod_amd.layers import operand_cache
     from wsovod_amd.testing import build_hot_path_model
 
     monkeypatch.setattr(H, "DETERMINISTIC", True)
@@ -122,13 +123,14 @@ def _steps(gpu, monkeypatch, fused, graph, precision, n_steps=6):
            "mom_fc1": tr.optimizer.state[fc1]["momentum_buffer"].clone(), "losses": losses, "calls": calls,
            "graphs": len(tr._graphs)}
     if precision == "parity":  # the operand copy the NEXT forward reads must be the encoding of the weight as it stands
-        xe = getattr(fc1, "_x2_enc", None)
-        assert xe is not None and xe[0] == (fc1._version, fc1.data_ptr(), None)
-        assert torch.equal(xe[1], H.x2_encode(fc1.detach()))
+        xe = operand_cache.current(fc1, "x2")
+        assert xe is not None and operand_cache.refreshable(fc1)[1] is xe
+        assert torch.equal(xe, H.x2_encode(fc1.detach()))
     if precision == "parity_mx":  # likewise the f16mx operand (one scale for the tensor, refreshed by the update kernels)
-        me = getattr(fc1, "_mx_enc", None)
-        assert me is not None and me[0] == (fc1._version, fc1.data_ptr(), None) and me[2]
-        assert torch.equal(me[1][0].view(torch.int32), H.mx_encode(fc1.detach(), tensor_byte=fc1._mx_scale)[0].view(torch.int32))
+        me, byte = operand_cache.current(fc1, "mx"), operand_cache.scale_byte(fc1)
+        fmt, sh = operand_cache.refreshable(fc1)  # ("mx": current AND encoded with the one scale for the tensor)
+        assert me is not None and fmt == "mx" and sh[0] is me[0] and sh[1] is byte
+        assert torch.equal(me[0].view(torch.int32), H.mx_encode(fc1.detach(), tensor_byte=byte)[0].view(torch.int32))
     tr.close()
     assert not hasattr(fc1, "_fused_update")
     return out

@@ -185,10 +185,10 @@ def test_whole_step_graph_reproduces_the_eager_steps(gpu, monkeypatch, precision
             assert model.roi_heads.box_head._step == len(batches) and tr.iter == len(batches)
             assert int(model.roi_heads.box_head._step_dev) == 16 * len(batches)
             if precision == "parity_mx":  # the replays refreshed fc1 / fc2's f16mx operands: their caches stay current
-                from wsovod_amd.engine.trainer import _mx_shadow
+                from wsovod_amd.layers.operand_cache import refreshable
 
                 bh = model.roi_heads.box_head
-                assert _mx_shadow(bh.fc1.weight) is not None and _mx_shadow(bh.fc2.weight) is not None
+                assert refreshable(bh.fc1.weight)[0] == "mx" and refreshable(bh.fc2.weight)[0] == "mx"
         else:
             assert not tr._graphs
         tr.flush()
@@ -391,6 +391,7 @@ def test_replays_keep_the_f16mx_weight_cache_current(gpu, monkeypatch):
     from wsovod_amd.engine import HotPathTrainer, build_optimizer
     from wsovod_amd.engine.trainer import _StepGraph
     from wsovod_amd.layers import hip_ops as H
+    from wsovod_amd.layers import operand_cache
     from wsovod_amd.modeling.backbone import ResNet
     from wsovod_amd.modeling.roi_heads import WSOVODROIHeads
     from wsovod_amd.testing import build_hot_path_model
@@ -434,9 +435,9 @@ def test_replays_keep_the_f16mx_weight_cache_current(gpu, monkeypatch):
     assert len(tr._graphs) == 2
     assert encodes == [], encodes
     for w in fcs:
-        me = w._mx_enc
-        assert me[0] == (w._version, w.data_ptr(), None)
-        assert torch.equal(me[1][0].view(torch.int32), encode(w.detach(), tensor_byte=w._mx_scale)[0].view(torch.int32))
+        me, byte = operand_cache.current(w, "mx"), operand_cache.scale_byte(w)
+        assert me is not None
+        assert torch.equal(me[0].view(torch.int32), encode(w.detach(), tensor_byte=byte)[0].view(torch.int32))
     tr.close()
 
 

@@ -241,6 +241,7 @@ def test_multi_tensor_sgd_matches_torch_sgd(gpu):
     """One launch for many tensors (odd sizes, misaligned tails, per-tensor lr / weight decay, bf16 shadows, >32
     tensors -> two launches) against torch.optim.SGD with the same groups."""
     from wsovod_amd.engine import HipSGD
+    from wsovod_amd.layers import operand_cache
 
     torch.manual_seed(1)
     sizes = [1, 3, 4, 5, 4095, 4096, 4097, 100003, 20, 512 * 1024] + [7 + i for i in range(30)]
@@ -252,7 +253,7 @@ def test_multi_tensor_sgd_matches_torch_sgd(gpu):
     shadows = {}
     for i in (5, 7, 9):  # bf16 shadows as the MFMA layers keep them
         shadows[i] = torch.empty(sizes[i], dtype=torch.bfloat16, device=gpu)
-        hips[i]._hip_shadow = (shadows[i], hips[i]._version)
+        operand_cache.lookup(hips[i], "bf16", lambda src, i=i: shadows[i], variant=torch.bfloat16)
     for step in range(3):
         for r, h in zip(refs, hips):
             g = torch.randn_like(r)
@@ -265,7 +266,7 @@ def test_multi_tensor_sgd_matches_torch_sgd(gpu):
         torch.testing.assert_close(h.detach().cpu(), r.detach(), rtol=1e-6, atol=1e-7, msg=lambda m: f"tensor {i}: {m}")
     for i, sh in shadows.items():
         assert torch.equal(sh.cpu(), hips[i].detach().to(torch.bfloat16).cpu())
-        assert hips[i]._hip_shadow[1] == hips[i]._version  # still valid: no re-cast on the next forward
+        assert operand_cache.current(hips[i], "bf16", variant=torch.bfloat16) is sh  # still valid: no re-cast on the next forward
 
 
 def test_eval_inference_runs(gpu):

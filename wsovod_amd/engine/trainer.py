@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from ..layers import hip_ops as H
+from ..layers import operand_cache
 
 
 class HipSGD(torch.optim.Optimizer):
@@ -46,16 +47,12 @@ class HipSGD(torch.optim.Optimizer):
                 if "momentum_buffer" not in state:
                     state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 g = wire if wire is not None else (p.grad if p.grad.is_contiguous() else p.grad.contiguous())
-                sh = getattr(p, "_hip_shadow", None)  # bf16 copy used by the MFMA kernels: refreshed in the same pass
-                shadow = sh[0] if (sh is not None and sh[1] == p._version and sh[0].dtype == torch.bfloat16) else None
-                xe = getattr(p, "_x2_enc", None)  # "parity" precision: the bf16x2 operand (hip_ops.x2_cached) instead
-                if xe is not None and xe[0] == (p._version, p.data_ptr(), None) and p.numel() % 32 == 0:
-                    shadow = xe[1]
-                shadow = _mx_shadow(p) or shadow  # "parity_mx": the f16mx operand (hip_ops.mx_cached, one scale per tensor)
+                # the operand copy the kernels read (bf16 shadow, bf16x2 or one-scale f16mx): refreshed in the same pass
+                fmt, shadow = operand_cache.refreshable(p)
                 lr = group["lr"] if self.lr_device is None else self.lr_device[p]
                 by_momentum.setdefault(group["momentum"], []).append(
                     (p.data, g, state["momentum_buffer"], shadow, lr, group["weight_decay"],
-                     getattr(p, "_used_flag", None), p))
+                     getattr(p, "_used_flag", None), p, fmt))
         if self.clip is not None and self.clip[0] == "full_model" and len(by_momentum) > 1:
             raise NotImplementedError("HipSGD: full-model clipping needs one momentum value for all parameter groups")
         for mu, entries in by_momentum.items():  # every tensor of the model in one launch
@@ -63,32 +60,8 @@ class HipSGD(torch.optim.Optimizer):
                                                        clip=self.clip)
             for e in entries:
                 # the kernel wrote through raw pointers: advance the version counter so that caches keyed on it (folded
-                # conv weights, class matrices) are rebuilt, and re-stamp the bf16 shadow the kernel refreshed itself
-                p, shadow = e[7], e[3]
-                torch.autograd.graph.increment_version(p)
-                _restamp_shadow(p, shadow)
-
-
-def _mx_shadow(p):
-    """(f16mx carrier, per-tensor E8M0 byte) of a parameter whose CURRENT f16mx operand was encoded with one scale for the
-    tensor (hip_ops.mx_cached(tensor_scale=True): the FC weights under "parity_mx"), else None: the update kernels re-encode
-    it element-wise in their pass."""
-    me = getattr(p, "_mx_enc", None)
-    if me is None or len(me) < 3 or not me[2] or me[0] != (p._version, p.data_ptr(), None) or p.numel() % 32:
-        return None
-    byte = getattr(p, "_mx_scale", None)
-    return (me[1][0], byte) if byte is not None else None
-
-
-def _restamp_shadow(p, shadow):
-    """After an update kernel refreshed `shadow` through raw pointers: the operand cache of the parameter carries its new
-    version (a stale second format, if the parameter has one, stays behind and is re-encoded at its next use)."""
-    if isinstance(shadow, tuple):
-        p._mx_enc = ((p._version, p.data_ptr(), None), p._mx_enc[1], True)
-    elif shadow is not None and shadow.dtype == torch.float32:
-        p._x2_enc = ((p._version, p.data_ptr(), None), shadow)
-    elif shadow is not None:
-        p._hip_shadow = (shadow, p._version)
+                # conv weights, class matrices) are rebuilt, and re-stamp the operand the kernel refreshed itself
+                operand_cache.wrote(e[7], e[8])
 
 
 class _FusedUpdate:
@@ -135,17 +108,11 @@ class _FusedUpdate:
         state = opt.state[p]
         if "momentum_buffer" not in state:
             state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        sh = getattr(p, "_hip_shadow", None)
-        shadow = sh[0] if (sh is not None and sh[1] == p._version and sh[0].dtype == torch.bfloat16) else None
-        xe = getattr(p, "_x2_enc", None)
-        if xe is not None and xe[0] == (p._version, p.data_ptr(), None) and p.numel() % 32 == 0:
-            shadow = xe[1]
-        shadow = _mx_shadow(p) or shadow
+        fmt, shadow = operand_cache.refreshable(p)
         lr = g["lr"] if opt.lr_device is None else opt.lr_device[p]
         H.gemm_tn_sgd(dA, x, p.data, state["momentum_buffer"], shadow, lr, g["weight_decay"], g["momentum"],
                       grad_scale=opt.grad_scale, q_x2=q_x2)
-        torch.autograd.graph.increment_version(p)  # (as HipSGD.step: caches keyed on the version are rebuilt ...
-        _restamp_shadow(p, shadow)                 # ... and the refreshed operand copy is re-stamped)
+        operand_cache.wrote(p, fmt)  # (as HipSGD.step: the version advances, the refreshed operand is re-stamped)
         self.calls += 1
         return True
 
@@ -659,8 +626,9 @@ class HotPathTrainer:
         if self.exchange:
             for t in list(self.model.parameters()) + list(self.model.buffers()):
                 dist.broadcast(t.data, src)
-                # the broadcast wrote through `.data`: bump the version counter so that caches keyed on it (bf16 / bf16x2
-                # shadows, folded conv weights, class matrices) are rebuilt from the received values
+                # the broadcast wrote through `.data`: bump the version counter so that caches keyed on it (the weight
+                # operands of layers/operand_cache.py, folded conv weights, class matrices) are rebuilt from the received
+                # values
                 torch.autograd.graph.increment_version(t)
 
     def set_exchange(self, algo):
@@ -1064,24 +1032,13 @@ class HotPathTrainer:
     def _graph_bookkeeping(self):
         """The host-side state one eager step advances, mirrored for a replay (no Python model code runs then): the
         dropout step counters (their device terms advance inside the graph), the heads' iteration, the parameters'
-        version counters (caches keyed on them) and the stamps of the shadows the SGD kernel refreshed."""
+        version counters (caches keyed on them) and the stamps of the operands the SGD kernel refreshed."""
         rh = self.model.roi_heads
         rh.iter += 1
         for m in self._counters()[0]:
             m[0]._step += 1
         for p in self.params:
-            sh = getattr(p, "_hip_shadow", None)
-            xe = getattr(p, "_x2_enc", None)
-            stamped = sh is not None and sh[1] == p._version
-            stamped_x = xe is not None and xe[0] == (p._version, p.data_ptr(), None)
-            stamped_mx = _mx_shadow(p) is not None  # (the f16mx operand the captured SGD launch refreshes)
-            torch.autograd.graph.increment_version(p)
-            if stamped:
-                p._hip_shadow = (sh[0], p._version)
-            if stamped_x:
-                p._x2_enc = ((p._version, p.data_ptr(), None), xe[1])
-            if stamped_mx:
-                p._mx_enc = ((p._version, p.data_ptr(), None), p._mx_enc[1], True)
+            operand_cache.replayed(p)
 
     def run_step(self, data):
         g = self._graph_for(data)

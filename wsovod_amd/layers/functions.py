@@ -12,6 +12,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip_ops as H
+from . import operand_cache
 
 
 _USE_TN = os.environ.get("WSOVOD_DISABLE_TN", "0") != "1"  # A/B switch for the transposed-read dW kernel
@@ -35,19 +36,13 @@ def _contig2d(t):
 
 
 def weight_shadow(weight, cd):
-    """Compute-dtype copy of an fp32 master weight.  For leaf parameters the bf16 copy is cached on the
-    parameter (`_hip_shadow` = (tensor, version)); HipSGD refreshes it inside the fused update kernel, so in
-    steady state no separate cast pass over the weights runs.  Any other in-place change of the parameter
-    bumps `_version` and invalidates the cache."""
+    """Compute-dtype copy of an fp32 master weight.  For leaf parameters the copy is cached on the parameter
+    (operand_cache, format "bf16"); HipSGD refreshes a bf16 one inside the fused update kernel, so in steady state
+    no separate cast pass over the weights runs.  Any other in-place change of the parameter bumps `_version`
+    and invalidates the cache."""
     if cd == torch.float32:
         return weight
-    sh = getattr(weight, "_hip_shadow", None)
-    if sh is not None and sh[1] == weight._version and sh[0].dtype == cd:
-        return sh[0]
-    t = H.cast(weight.detach(), cd)
-    if weight.is_leaf:
-        weight._hip_shadow = (t, weight._version)
-    return t
+    return operand_cache.lookup(weight, "bf16", lambda src: H.cast(src, cd), variant=cd, store=weight.is_leaf)
 
 
 def _x2_mode():

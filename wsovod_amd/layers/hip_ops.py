@@ -12,6 +12,7 @@ import torch
 
 from .. import _lib
 from .._lib import BF16, BF16X2, BF16X2P, F16MX, F32, NCHW, NHWC, GemmDesc, check, dtype_code, lib, ptr, require_gpu, stream
+from . import operand_cache
 
 
 _CONST_CACHE = {}
@@ -551,22 +552,26 @@ MX_WEIGHT_HEADROOM = 1  # binades between a trained weight's largest magnitude a
 def mx_tensor_scale(t):
     """The per-tensor E8M0 byte (1-element uint8 DEVICE tensor) of a TRAINED weight's f16mx operand, derived from the tensor's
     largest magnitude (+ MX_WEIGHT_HEADROOM binades) without a host read at every FULL encode of the weight (the first use, a
-    loaded checkpoint) and written IN PLACE into the tensor kept on the parameter (`_mx_scale`: captured step graphs and the
-    optimizer's table keep its address).  Between full encodes the scale is fixed and the optimizer kernels re-encode the
+    loaded checkpoint) and written IN PLACE into the tensor kept on the parameter (operand_cache.scale_byte: captured step
+    graphs and the optimizer's table keep its address).  Between full encodes the scale is fixed and the optimizer kernels re-encode the
     operand element-wise inside their update pass; e4m3's own exponent carries the rows and the growth of the weights
     (beyond 448 / 256 x 2^headroom of that maximum the cross terms saturate: their accuracy goes, not the product's)."""
     amax = t.detach().abs().amax().float().clamp_(min=2.0 ** -14)
     byte = (torch.floor(torch.log2(amax)) - 7 + MX_WEIGHT_HEADROOM + 127).clamp_(1, 254).to(torch.uint8).reshape(1)
-    s = getattr(t, "_mx_scale", None)
-    if s is None:
-        s = byte
-        try:
-            t._mx_scale = s
-        except AttributeError:
-            pass
+    return operand_cache.scale_byte(t, byte)
+
+
+def _encode_one_scale_mx(t, src):
+    byte = mx_tensor_scale(t)
+    old = operand_cache.one_scale_mx(t)
+    if old is not None and old[0].shape == src.shape:
+        car, scales = old  # (re-encoded in place: a captured graph / the optimizer's table keep the addresses)
     else:
-        s.copy_(byte)
-    return s
+        car = torch.empty_like(src)
+        scales = torch.empty((src.shape[0], 1), dtype=torch.uint8, device=src.device)
+    check(lib().wsovod_f16mx_encode_with(ptr(src), src.stride(0), src.shape[0], src.shape[1], ptr(car), car.stride(0),
+                                         ptr(scales), ptr(byte), stream()), "f16mx_encode_with")
+    return car, scales
 
 
 def mx_cached(t, view_rows_cols=None, tensor_scale=False):
@@ -574,48 +579,15 @@ def mx_cached(t, view_rows_cols=None, tensor_scale=False):
     backbone weights: once, with their own row scales).  tensor_scale (trained weights): ONE scale for the tensor
     (mx_tensor_scale) -- the optimizer then refreshes the carrier in its update pass and re-stamps the cache, so that in steady
     state no encode pass runs."""
-    key = (t._version, t.data_ptr(), view_rows_cols)
-    c = getattr(t, "_mx_enc", None)
-    if c is not None and c[0] == key:
-        return c[1]
-    src = t.detach()
-    if tensor_scale and view_rows_cols is None and src.dim() == 2 and src.is_contiguous() and src.shape[1] % 32 == 0:
-        byte = mx_tensor_scale(t)
-        if c is not None and len(c) > 2 and c[2] and c[1][0].shape == src.shape:
-            car, scales = c[1]  # (re-encoded in place: a captured graph / the optimizer's table keep the addresses)
-        else:
-            car = torch.empty_like(src)
-            scales = torch.empty((src.shape[0], 1), dtype=torch.uint8, device=src.device)
-        check(lib().wsovod_f16mx_encode_with(ptr(src), src.stride(0), src.shape[0], src.shape[1], ptr(car), car.stride(0),
-                                             ptr(scales), ptr(byte), stream()), "f16mx_encode_with")
-        out = (car, scales)
-        try:
-            t._mx_enc = (key, out, True)  # (True: ONE scale for the tensor -- what the optimizer kernels can refresh)
-        except AttributeError:
-            pass
-        return out
-    out = mx_encode(src.reshape(view_rows_cols) if view_rows_cols is not None else src)
-    try:
-        t._mx_enc = (key, out, False)
-    except AttributeError:
-        pass
-    return out
+    one = tensor_scale and view_rows_cols is None and t.dim() == 2 and t.is_contiguous() and t.shape[1] % 32 == 0
+    return operand_cache.lookup(t, "mx", (lambda src: _encode_one_scale_mx(t, src)) if one else mx_encode, view_rows_cols,
+                                one_scale=one)
 
 
 def x2_cached(t, view_rows_cols=None):
     """bf16x2 encoding of a weight, cached on the tensor object and keyed by its version counter (one re-encode per
     optimizer step at most; frozen backbone weights once)."""
-    key = (t._version, t.data_ptr(), view_rows_cols)
-    c = getattr(t, "_x2_enc", None)
-    if c is not None and c[0] == key:
-        return c[1]
-    src = t.detach()
-    out = x2_encode(src.reshape(view_rows_cols) if view_rows_cols is not None else src)
-    try:
-        t._x2_enc = (key, out)
-    except AttributeError:
-        pass
-    return out
+    return operand_cache.lookup(t, "x2", x2_encode, view_rows_cols)
 
 
 def stem_conv1_x2(images_u8, sizes, mean, std, w32_x2, bias):
@@ -726,17 +698,7 @@ def split3_bf16(src, side, stack_rows=False, rows_pad=None, out=None):
 def _split3_cached(t, side, view_rows_cols=None):
     """B-side operands are usually weights: the split is cached on the tensor object, keyed by its version counter
     (HipSGD bumps it after every update), so steady-state forwards re-split a weight once per step at most."""
-    key = (t._version, t.data_ptr(), side, view_rows_cols)
-    c = getattr(t, "_x3_split", None)
-    if c is not None and c[0] == key:
-        return c[1]
-    src = t.detach()
-    out = split3_bf16(src.reshape(view_rows_cols) if view_rows_cols is not None else src, side)
-    try:
-        t._x3_split = (key, out)
-    except AttributeError:
-        pass
-    return out
+    return operand_cache.lookup(t, "x3", lambda src: split3_bf16(src, side), view_rows_cols, variant=side)
 
 
 def _gemm_nt_x3(A, B, conv=None, **kw):

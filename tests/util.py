@@ -20,3 +20,36 @@ def random_rois(R, n_img, H_img, W_img, seed=0, edge_cases=True):
         rois[6, 1:] = torch.tensor([3.5, 3.5, 12.5, 20.5])  # .5 rounding (half away from zero)
         rois[7, 1:] = torch.tensor([W_img + 50.0, H_img + 50.0, W_img + 90.0, H_img + 90.0])  # fully outside
     return rois
+
+
+# ---- input builders of tests/test_gpu_elementwise.py ---------------------------------------------------------------
+SENTINEL = -7777.0  # (rounded to the buffer's dtype when it is filled; compared through the same rounding)
+
+
+def bits(t):
+    """Integer view of a float tensor: comparisons through it count NaN payloads and the sign of zero."""
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+
+
+def odd_view(shape, dtype, ld, offset, device, tail=11):
+    """((rows, cols) view with row stride ld >= cols, its buffer): the view starts `offset` elements into a flat buffer
+    pre-filled with SENTINEL, which forces the kernels' non-16-byte-aligned / odd-leading-dimension paths."""
+    rows, cols = shape
+    assert ld >= cols and rows >= 1
+    buf = torch.full((offset + (rows - 1) * ld + cols + tail,), SENTINEL, dtype=dtype, device=device)
+    return buf.as_strided((rows, cols), (ld, 1), offset), buf
+
+
+def outside_intact(buf, view):
+    """True when every element of `buf` outside `view` (an odd_view of it, or any 2-D strided view) still holds SENTINEL."""
+    rows, cols = view.shape
+    off = view.storage_offset() - buf.storage_offset()
+    inside = torch.zeros(buf.numel(), dtype=torch.bool)
+    idx = off + torch.arange(rows)[:, None] * view.stride(0) + torch.arange(cols)[None, :] * view.stride(1)
+    inside[idx.reshape(-1)] = True
+    rest = buf.detach().reshape(-1).cpu()[~inside]
+    return bool((bits(rest) == bits(torch.full((1,), SENTINEL, dtype=buf.dtype))).all())

@@ -212,7 +212,7 @@ class _StepMeta:
         return buf[off:off + count * torch.empty((), dtype=dt).element_size()].view(dt)
 
     def image_level_gt(self):
-        return self.gt_cat, self.gt_off, self.onehot
+        return self.gt_cat, self.gt_off, self.onehot, self.MAX_CLASSES_PER_IMAGE  # (fill() turns longer lists away)
 
     def overrides(self, nums):
         """{(values, dtype): static tensor} for hip_ops.const_override while the step is captured.  `nums`: the per-image

@@ -1089,13 +1089,29 @@ def weighted_l1_box_forward(pred, proposal_boxes, gt_boxes, gt_classes, weights,
     return loss, dp
 
 
-def pgt_mine_and_label(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, img_scores, K, iou_threshold):
-    """See include/wsovod_hip.h.  Returns a dict of device tensors."""
+PGT_MAX_CLASSES = 128  # == kMaxPgt of pgt_mine_label_kernel (csrc/heads.hip): image-level GT classes one image may carry
+
+
+def pgt_mine_and_label(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, img_scores, K, iou_threshold,
+                       max_gt_per_image=None):
+    """See include/wsovod_hip.h.  Returns a dict of device tensors.
+    max_gt_per_image: the longest per-image class list, a HOST int from where the lists were built.  The kernel keeps an
+    image's first PGT_MAX_CLASSES classes in LDS and would drop the rest without a word, so more is refused here.  Without
+    it the bound min(K, T) decides (an image's list is sorted-unique: at most K long, and no longer than all lists
+    together); only when that leaves the question open are the offsets read back (one synchronisation)."""
     require_gpu(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, img_scores)
     dev = scores.device
     M = scores.size(0)
     G = seg_offsets.numel() - 1
     T = gt_classes_img.numel()
+    if max_gt_per_image is None:
+        max_gt_per_image = min(int(K), T)
+        if max_gt_per_image > PGT_MAX_CLASSES and G > 0:
+            max_gt_per_image = int((gt_offsets[1:] - gt_offsets[:-1]).max())
+    if max_gt_per_image > PGT_MAX_CLASSES:
+        raise RuntimeError(f"wsovod_hip pgt_mine_and_label: an image carries {int(max_gt_per_image)} image-level GT classes, the "
+                           f"mining kernel holds {PGT_MAX_CLASSES} per image (kMaxPgt); the classes beyond would get no pseudo "
+                           "ground truth")
     zero = torch.zeros((32 * T + 4 * G,), dtype=torch.uint8, device=dev)  # one fill for the five zero-initialised outputs
     o = dict(
         pgt_boxes=zero[:16 * T].view(torch.float32).view(T, 4),

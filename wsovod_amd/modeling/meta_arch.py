@@ -174,7 +174,7 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
             oh[i, u] = 1.0
         cat = H.h2d_small(torch.cat(cls_list), self.device)
         off = segment_offsets([len(u) for u in cls_list], self.device)
-        return cat, off, H.h2d_small(oh, self.device)
+        return cat, off, H.h2d_small(oh, self.device), max([len(u) for u in cls_list], default=0)
 
     def forward(self, batched_inputs, classifier=None):
         if not self.training:

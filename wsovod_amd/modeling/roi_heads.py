@@ -149,7 +149,7 @@ class WSOVODROIHeads(ROIHeads):
         self.metadata = metadata
         self.precision = precision
         self.proposal_targets = None
-        self.image_level_gt = None  # optional (cls_cat int64, offsets int32, onehot) precomputed without syncs
+        self.image_level_gt = None  # optional (cls_cat int64, offsets int32, onehot, longest list) precomputed without syncs
 
     @property
     def compute_dtype(self):
@@ -237,12 +237,13 @@ class WSOVODROIHeads(ROIHeads):
         if self.training:
             assert targets, "'targets' argument is required during training"
             if self.image_level_gt is not None:
-                self._gt_cat, self._gt_off, self.gt_classes_img_oh = self.image_level_gt
+                self._gt_cat, self._gt_off, self.gt_classes_img_oh, self._gt_max = self.image_level_gt
                 self.image_level_gt = None
             else:  # drop-in path: host round trip (torch.unique sizes), as in the reference
                 _, gt_int, self.gt_classes_img_oh = get_image_level_gt(targets, self.num_classes)
                 self._gt_cat = torch.cat(gt_int)
                 self._gt_off = segment_offsets([len(g) for g in gt_int], self._gt_cat.device)
+                self._gt_max = max([len(g) for g in gt_int], default=0)  # (host ints: the mining kernel's per-image cap)
             # The reference first labels proposals against the dataset boxes
             # (label_and_sample_proposals, roi_heads.py:664); with weak supervision every field it
             # sets is overwritten by label_and_sample_proposals_wsl before any loss reads it, so
@@ -392,7 +393,7 @@ class WSOVODROIHeads(ROIHeads):
         (`.packed`); the per-image Instances of the reference's interface are cut only if somebody indexes the
         list (one host read of the counts)."""
         o = H.pgt_mine_and_label(prev_pred_scores.to(torch.float32), prev_pred_boxes, seg, self._gt_cat, self._gt_off,
-                                 self.pred_class_img_logits, self.num_classes, 0.5)
+                                 self.pred_class_img_logits, self.num_classes, 0.5, max_gt_per_image=self._gt_max)
         return PseudoTargets(o, self._gt_off, [p.image_size for p in proposals])
 
     def _sample_keys(self, num_rows, device):
@@ -412,7 +413,8 @@ class WSOVODROIHeads(ROIHeads):
         m = self.proposal_matchers[k]
         assert len(m.thresholds) == 3 and m.labels == [0, 1], "hot path supports Matcher([thr], [0, 1])"
         o = H.pgt_mine_and_label(prev_pred_scores.to(torch.float32), prev_pred_boxes, seg, self._gt_cat,
-                                 self._gt_off, self.pred_class_img_logits, self.num_classes, m.thresholds[1])
+                                 self._gt_off, self.pred_class_img_logits, self.num_classes, m.thresholds[1],
+                                 max_gt_per_image=self._gt_max)
         if max(nums) > self.batch_size_per_images[k] or self.positive_sample_fractions[k] < 1.0:
             # _sample_proposals_wsl (roi_heads.py:1597-1610): rows outside the random sample are ignored (-1); every
             # row stays in place, so the boxes / scores / weights above are untouched

@@ -1040,7 +1040,6 @@ def test_bf16x2_kernels_refuse_f16mx_carriers(gpu):
 
     x = torch.randn(64, 64, device=gpu)
     car, _ = H.mx_encode(x, unit=True)
-    car._mx = True
     x2 = H.x2_encode(x)
     view = car.view(64, 64)  # (a whole view carries the tag too)
     for kw in (dict(A=car, B=x2), dict(A=x2, B=view), dict(A=x2, B=x2, residual=car, residual_x2=True)):

@@ -112,11 +112,8 @@ class _Linear(Function):
             if out_dtype == H.MX and grad_on and any(ctx.needs_input_grad):
                 y_bf16 = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.bfloat16, device=x.device)
             y = H.gemm_mx(x, None, wq, wscale, bias=bias, relu=relu, dropout_p=dropout_p, dropout_seed=seed,
-                          dropout_seed_add=seed_add, out_dtype=out_dtype, out_bf16=y_bf16)
-            if out_dtype == H.MX:
-                y._mx = True
-                if y_bf16 is not None:
-                    y._x2_hi = y_mask = y_bf16
+                          dropout_seed_add=seed_add, out_dtype=out_dtype, out_bf16=y_bf16)  # (tagged MX, y_bf16 attached)
+            y_mask = y_bf16
             x_hi = H.x2_hi_pop(x)
             if x_hi is None and grad_on and ctx.needs_input_grad[1]:
                 raise RuntimeError("wsovod_hip linear: an f16mx input needs its plain bf16 copy for the weight gradient "

@@ -12,7 +12,7 @@ import torch
 
 from .. import _lib
 from .._lib import BF16, BF16X2, BF16X2P, F16MX, F32, NCHW, NHWC, GemmDesc, check, dtype_code, lib, ptr, require_gpu, stream
-from . import operand_cache
+from . import carrier, operand_cache
 
 
 _CONST_CACHE = {}
@@ -191,24 +191,9 @@ def format_rois(boxes, seg_offsets, objectness=None):
 def x2_hi_pop(x):
     """The plain bf16 rounding the pooler wrote next to the bf16x2 tensor `x` (or None): the first FC layer keeps it for
     its weight-gradient contraction, which would otherwise fetch half lines out of the bf16x2 rows.  The copy rides on
-    the pooled tensor OBJECT (and on the views the box head makes of it: `x2_hi_of`), never on a pointer-keyed table."""
-    hi = x2_hi_of(x)
+    the pooled tensor OBJECT (and on the views the box head makes of it: `carrier.hi_of`), never on a pointer-keyed table."""
+    hi = carrier.hi_of(x)
     return hi if (hi is not None and hi.numel() == x.numel()) else None
-
-
-def x2_hi_of(x):
-    """The bf16 copy attached to `x` or to the tensor `x` is a view of (flatten / view keep `_base`)."""
-    hi = getattr(x, "_x2_hi", None)
-    if hi is None and getattr(x, "_base", None) is not None and x._base.data_ptr() == x.data_ptr() \
-            and x._base.numel() == x.numel():
-        hi = getattr(x._base, "_x2_hi", None)
-    return hi
-
-
-def _x2_hi_alloc(out):
-    hi = torch.empty(out.shape, dtype=torch.bfloat16, device=out.device)
-    out._x2_hi = hi
-    return hi
 
 
 def _x2_planar_ok(R, row_values):
@@ -218,44 +203,28 @@ def _x2_planar_ok(R, row_values):
     return X2_PLANAR and (R * row_values) % 8 == 0 and (R + 256) * row_values * 2 < (1 << 31)
 
 
-def _x2_planar_tag(out):
-    """`out` (an fp32-typed carrier) was written as PLANAR bf16x2 (include/wsovod_hip.h: WSOVOD_BF16X2P): its first half is
-    the bf16 matrix of hi values -- attached as the tensor's plain bf16 rounding (`x2_hi_of`), no copy -- its second half
-    the lo values.  The first FC layer's forward reads both planes, its weight gradient the hi plane."""
-    n = out.numel()
-    out._x2_hi = out.view(-1).view(torch.bfloat16)[:n].view(out.shape)
-    out._x2_planar = True
-    return out
+def _tag_pooled(out, out_dtype, planar, hi):
+    """What a pooler wrote into `out`: a carrier (X2 / MX) is tagged, with `hi` as its plain bf16 rounding.  PLANAR bf16x2
+    (include/wsovod_hip.h: WSOVOD_BF16X2P): the first half of `out` IS the bf16 matrix of hi values -- attached, no copy --
+    its second half the lo values; the first FC layer's forward reads both planes, its weight gradient the hi plane."""
+    if planar:
+        hi = out.view(-1).view(torch.bfloat16)[:out.numel()].view(out.shape)
+    return carrier.tag(out, carrier.X2P if planar else out_dtype, hi) if out_dtype in (X2, MX) else out
+
+
+# the format of a float32-typed carrier is recorded on the tensor object: layers/carrier.py owns that protocol
+X2, MX = carrier.X2, carrier.MX  # format tags accepted wherever a kernel front takes an `out_dtype` (X2: or an `x2=`) argument
+x2_hi_of = carrier.hi_of
 
 
 def x2_planar_of(x):
     """True when `x` (or the tensor it is a whole view of) is a planar bf16x2 carrier."""
-    if x is None or x.dtype != torch.float32:
-        return False  # (a carrier is float32-typed: the bf16 view of its hi plane is a plain bf16 matrix)
-    if getattr(x, "_x2_planar", False):
-        return True
-    b = getattr(x, "_base", None)
-    return bool(b is not None and b.data_ptr() == x.data_ptr() and b.numel() == x.numel() and getattr(b, "_x2_planar", False))
+    return carrier.fmt_of(x) == carrier.X2P
 
 
-def _refuse_undeclared_planar(who, *tensors, declared=False):
-    """The planar layout changes what the BYTES of a carrier mean and is recorded on the tensor object only: a consumer that
-    reads interleaved bf16x2 must refuse a planar carrier instead of contracting garbage."""
-    if declared:
-        return
-    for t in tensors:
-        if t is not None and x2_planar_of(t):
-            raise RuntimeError(f"wsovod_hip {who}: got a PLANAR bf16x2 carrier where the interleaved layout is read "
-                               "(only the first FC layer's forward takes a_planar=True; x2_to_f32 decodes either layout)")
-
-
-def _refuse_mx(who, *tensors):
-    """An f16mx carrier is float32-typed and 4 bytes per value like bf16x2, and its format is recorded on the tensor object
-    only (`mx_of`): a consumer that reads bf16x2 or plain fp32 must refuse it instead of contracting its bytes."""
-    for t in tensors:
-        if t is not None and mx_of(t):
-            raise RuntimeError(f"wsovod_hip {who}: got an f16mx carrier where bf16x2 / fp32 values are read "
-                               "(f16mx operands go to gemm_mx)")
+def mx_of(x):
+    """True when `x` (or the tensor it is a whole view of) was written as a unit-scale f16mx carrier."""
+    return carrier.fmt_of(x) == MX
 
 
 def x2_to_f32(x):
@@ -270,19 +239,6 @@ def x2_to_f32(x):
 # round 5: with `want_hi` (training, "parity") the poolers write PLANAR bf16x2 instead of the interleaved layout plus a plain
 # bf16 copy (WSOVOD_X2_PLANAR=0: the round-4 form, for A/B runs)
 # (only the LEAN two-phase tile reads the planar form: WSOVOD_G8_LEAN=0 therefore also selects the round-4 layout)
-MX = "f16mx"  # format tag of the block-scaled parity format (include/wsovod_hip.h: WSOVOD_F16MX); carriers are float32-typed
-
-
-def mx_of(x):
-    """True when `x` (or the tensor it is a whole view of) was written as a unit-scale f16mx carrier."""
-    if x is None or x.dtype != torch.float32:
-        return False
-    if getattr(x, "_mx", False):
-        return True
-    b = getattr(x, "_base", None)
-    return bool(b is not None and b.data_ptr() == x.data_ptr() and b.numel() == x.numel() and getattr(b, "_mx", False))
-
-
 X2_PLANAR = os.environ.get("WSOVOD_X2_PLANAR", "1") != "0" and os.environ.get("WSOVOD_G8_LEAN", "1") != "0"
 POISON_OUTPUTS = os.environ.get("WSOVOD_POISON_OUTPUTS", "0") == "1"
 POISON_BYTE = 0x7F
@@ -313,9 +269,8 @@ def roi_pool_forward(feat, rois, spatial_scale, output_size, roi_scale=None, out
     if roi_scale is not None:
         roi_scale = roi_scale.to(torch.float32).contiguous()
     planar = bool(want_hi and out_dtype == X2 and R > 0 and _x2_planar_ok(R, Cc * ph * pw))
-    hi = _x2_hi_alloc(out) if (want_hi and out_dtype in (X2, MX) and R > 0 and not planar) else None
-    if out_dtype == MX:
-        out._mx = True  # a unit-scale f16mx carrier (with, in training, its plain bf16 rounding for fc1's weight gradient)
+    # (an f16mx or interleaved bf16x2 output comes, in training, with its plain bf16 rounding for fc1's weight gradient)
+    hi = torch.empty_like(out, dtype=torch.bfloat16) if (want_hi and out_dtype in (X2, MX) and R > 0 and not planar) else None
     # scratch for the map's 2x2 maxima (0 bytes: this shape keeps the cell scan; include/wsovod_hip.h)
     ws_bytes = int(lib().wsovod_roi_pool_workspace_bytes(dtype_code(feat.dtype), layout, R, N, Cc, H, W, ph, pw,
                                                          int(need_argmax))) if R > 0 else 0
@@ -326,9 +281,7 @@ def roi_pool_forward(feat, rois, spatial_scale, output_size, roi_scale=None, out
         ptr(feat), dtype_code(feat.dtype), layout, ptr(rois), ptr(roi_scale), R, N, Cc, H, W, ph, pw,
         C.c_float(spatial_scale), ptr(out), BF16X2P if planar else fmt_code(out_dtype), ptr(argmax), ptr(hi),
         ptr(ws if m2 is None else m2), ws_bytes, stream()), "roi_pool_forward")
-    if planar:
-        _x2_planar_tag(out)
-    return out, argmax
+    return _tag_pooled(out, out_dtype, planar, hi), argmax
 
 
 def roi_loop_pool_forward(feat, rois, spatial_scale, output_size, context_ratio=1.8):
@@ -378,16 +331,12 @@ def roi_align_forward(feat, rois, spatial_scale, output_size, sampling_ratio, al
     if roi_scale is not None:
         roi_scale = roi_scale.to(torch.float32).contiguous()
     planar = bool(want_hi and out_dtype == X2 and R > 0 and _x2_planar_ok(R, Cc * ph * pw))
-    hi = _x2_hi_alloc(out) if (want_hi and out_dtype in (X2, MX) and R > 0 and not planar) else None
-    if out_dtype == MX:
-        out._mx = True
+    hi = torch.empty_like(out, dtype=torch.bfloat16) if (want_hi and out_dtype in (X2, MX) and R > 0 and not planar) else None
     check(lib().wsovod_roi_align_forward_x2hi(
         ptr(feat), dtype_code(feat.dtype), layout, ptr(rois), ptr(roi_scale), R, N, Cc, H, W, ph, pw,
         C.c_float(spatial_scale), int(sampling_ratio), int(bool(aligned)), ptr(out),
         BF16X2P if planar else fmt_code(out_dtype), ptr(hi), stream()), "roi_align_forward")
-    if planar:
-        _x2_planar_tag(out)
-    return out
+    return _tag_pooled(out, out_dtype, planar, hi)
 
 
 def roi_align_backward(grad_out, rois, spatial_scale, sampling_ratio, aligned, input_shape, channels_last=False,
@@ -412,15 +361,14 @@ def roi_align_backward(grad_out, rois, spatial_scale, sampling_ratio, aligned, i
 # shapes, strides and byte sizes as fp32, so views / flatten / autograd's shape checks all work, but its numbers are
 # meaningless to torch ops: only the kernels that take the `X2` format tag may read it.
 # ---------------------------------------------------------------------------------------
-X2 = "bf16x2"  # format tag accepted wherever a kernel front takes an `out_dtype` / `x2=` argument
 
 
 def storage_dtype(fmt):
-    return torch.float32 if fmt in (X2, "f16mx") else fmt
+    return torch.float32 if fmt in (X2, MX) else fmt
 
 
 def fmt_code(fmt):
-    return BF16X2 if fmt == X2 else F16MX if fmt == "f16mx" else dtype_code(fmt)
+    return BF16X2 if fmt == X2 else F16MX if fmt == MX else dtype_code(fmt)
 
 
 def x2_encode(src, out=None):
@@ -432,13 +380,13 @@ def x2_encode(src, out=None):
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=src.device)
     check(lib().wsovod_bf16x2_encode(ptr(src), src.stride(0), rows, cols, ptr(out), out.stride(0), stream()), "bf16x2_encode")
-    return out
+    return carrier.tag(out, X2)
 
 
 def x2_decode(src):
     """bf16x2 (rows, cols) -> the fp32 values hi + lo (tests, debugging)."""
     require_gpu(src)
-    _refuse_undeclared_planar("x2_decode", src)  # (x2_to_f32 reads either layout)
+    carrier.refuse("x2_decode", (src,), reads=(MX,))  # (planar: x2_to_f32 reads either layout)
     rows, cols = src.shape
     out = torch.empty((rows, cols), dtype=torch.float32, device=src.device)
     check(lib().wsovod_bf16x2_decode(ptr(src), src.stride(0), rows, cols, ptr(out), out.stride(0), stream()), "bf16x2_decode")
@@ -461,7 +409,7 @@ def mx_encode(src, nseg=1, unit=False, tensor_byte=None):
     scales = None if unit else torch.empty((rows, nseg), dtype=torch.uint8, device=src.device)
     check(lib().wsovod_f16mx_encode(ptr(src), src.stride(0), rows, cols, int(nseg), ptr(out), out.stride(0), ptr(scales),
                                     stream()), "f16mx_encode")
-    return out, scales
+    return (carrier.tag(out, MX) if unit else out), scales
 
 
 def mx_decode(carrier, scales=None):
@@ -487,11 +435,11 @@ def mx_to_f32(carrier):
 def mx_from_x2(src):
     """interleaved bf16x2 tensor -> unit-scale f16mx tensor of the same shape (wsovod_f16mx_from_bf16x2)."""
     require_gpu(src)
-    _refuse_undeclared_planar("mx_from_x2", src)
+    carrier.refuse("mx_from_x2", (src,), reads=(MX,))
     assert src.dtype == torch.float32 and src.is_contiguous() and src.shape[-1] % 32 == 0
     out = torch.empty_like(src)
     check(lib().wsovod_f16mx_from_bf16x2(ptr(src), ptr(out), src.numel(), stream()), "f16mx_from_bf16x2")
-    return out
+    return carrier.tag(out, MX)
 
 
 def gemm_mx(A, a_scale, B, b_scale, *, bias=None, relu=False, dropout_p=0.0, dropout_seed=0, dropout_seed_add=None,
@@ -543,7 +491,7 @@ def gemm_mx(A, a_scale, B, b_scale, *, bias=None, relu=False, dropout_p=0.0, dro
     check(lib().wsovod_gemm_f16mx(C.byref(d), ptr(a_scale), 1 if a_scale is None else int(a_scale.shape[1]), ptr(b_scale),
                                   int(b_scale.shape[1]), ptr(out_bf16), 0 if out_bf16 is None else _ld(out_bf16), stream()),
           "gemm_f16mx")
-    return out
+    return carrier.tag(out, out_dtype, out_bf16 if out_dtype == MX else None) if out_dtype in (X2, MX) else out
 
 
 MX_WEIGHT_HEADROOM = 1  # binades between a trained weight's largest magnitude at its first encode and the q plane's 256
@@ -599,7 +547,7 @@ def stem_conv1_x2(images_u8, sizes, mean, std, w32_x2, bias):
     out = torch.empty((N, Ho, Wo, 64), dtype=torch.float32, device=images_u8.device)
     check(lib().wsovod_stem_conv1_x2(ptr(images_u8), ptr(sizes), _f3(mean), _f3(std), N, Hp, Wp, ptr(w32_x2), ptr(bias),
                                      ptr(out), stream()), "stem_conv1_x2")
-    return out
+    return carrier.tag(out, X2)
 
 
 # ---------------------------------------------------------------------------------------
@@ -735,9 +683,9 @@ def gemm_nt(A, B, *, out=None, out_dtype=None, out_t=None, alpha=1.0, row_scale=
     Returns `out` (or None if want_c is False).
     """
     require_gpu(A, B, out, out_t, row_scale, bias, residual, row_group, group_add, mask_src)
-    _refuse_undeclared_planar("gemm_nt", A, declared=a_planar)
-    _refuse_undeclared_planar("gemm_nt", B, A2)
-    _refuse_mx("gemm_nt", A, B, A2, residual)
+    carrier.refuse("gemm_nt", (A,), reads=(carrier.X2P,) if a_planar else ())
+    carrier.refuse("gemm_nt", (B, A2))
+    carrier.refuse("gemm_nt", (residual,), reads=(carrier.X2P,))
     if x2 and (A.dtype != torch.float32 or B.dtype != torch.float32):
         raise RuntimeError("wsovod_hip gemm: bf16x2 operands travel as float32-typed tensors")
     if not x2 and _X3State.active and A.dtype == torch.float32 and B.dtype == torch.float32:
@@ -807,7 +755,7 @@ def gemm_nt(A, B, *, out=None, out_dtype=None, out_t=None, alpha=1.0, row_scale=
     d.accumulate = int(bool(accumulate))
     d.tile_hint = int(tile_hint)
     check(lib().wsovod_gemm_nt(C.byref(d), stream()), "gemm_nt")
-    return out
+    return carrier.tag(out, X2) if (want_c and d.dtype_c == BF16X2) else out
 
 
 # ---------------------------------------------------------------------------------------
@@ -859,7 +807,7 @@ def maxpool2x2_nhwc(x, stride, zero_pad_br=False, x2=False):
     out = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
     check(lib().wsovod_maxpool2x2_nhwc(ptr(x), BF16X2 if x2 else dtype_code(x.dtype), N, H, W, Cc, stride, int(zero_pad_br),
                                        ptr(out), stream()), "maxpool2x2_nhwc")
-    return out
+    return carrier.tag(out, X2) if x2 else out
 
 
 def maxpool2x2_nhwc_backward(x, dout, stride, zero_pad_br=False, x2=False):
@@ -1322,7 +1270,7 @@ def gemm_tn(P, Q, out=None, alpha=1.0, accumulate=False, split_tail=True, q_x2=F
     contraction over the operands' slow index, no transposed copies (transposed LDS reads).
     split_tail=False keeps a partial last round of tiles unsplit (fixed summation order, bit-reproducible)."""
     require_gpu(P, Q, out)
-    _refuse_undeclared_planar("gemm_tn", P, Q)  # (the hi plane of a planar carrier is passed as its own bf16 view)
+    carrier.refuse("gemm_tn", (P, Q), reads=(MX,))  # (the hi plane of a planar carrier is passed as its own bf16 view)
     split_tail = split_tail and not DETERMINISTIC
     # q_x2: Q is a bf16x2 matrix (fp32-typed carrier); the kernel reads the hi halves = Q rounded to bf16
     assert P.dtype == torch.bfloat16 and Q.dtype == (torch.float32 if q_x2 else torch.bfloat16) and P.shape[0] == Q.shape[0]
@@ -1351,7 +1299,7 @@ def gemm_tn_sgd(P, Q, param, momentum_buf, shadow, lr, weight_decay, momentum, g
     if isinstance(shadow, tuple):  # (f16mx carrier, per-tensor E8M0 byte): the "parity_mx" weight operand
         shadow, mx_byte = shadow
     require_gpu(P, Q, param, momentum_buf, shadow, mx_byte)
-    _refuse_undeclared_planar("gemm_tn_sgd", P, Q)
+    carrier.refuse("gemm_tn_sgd", (P, Q), reads=(MX,))
     assert P.dtype == torch.bfloat16 and Q.dtype == (torch.float32 if q_x2 else torch.bfloat16) and P.shape[0] == Q.shape[0]
     Mred, NI, NJ = P.shape[0], P.shape[1], Q.shape[1]
     if tuple(param.shape) != (NI, NJ) or not param.is_contiguous() or param.dtype != torch.float32 \

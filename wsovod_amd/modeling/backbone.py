@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import BACKBONE_REGISTRY
-from ..layers import hip_ops as H
+from ..layers import carrier, hip_ops as H
 from ..structures import ShapeSpec
 
 __all__ = ["BasicStem", "BasicBlock", "BottleneckBlock", "ResNet", "FrozenBatchNorm2d", "Conv2d",
@@ -137,28 +137,19 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
     if H.x3_active() in ("full", "fwd") and x.dtype == torch.float32:
         per_image = max(per_image, Hh * Ww * 3 * Cin * 2)  # the operand the kernel addresses is the [hi | hi | lo] bf16 split
     max_n = max(1, CONV_MAX_OPERAND_BYTES // max(per_image, 1))
-    # the format of the maps is decided once, before any split: f16mx is known only through the tensor object's tag, which a
-    # batch slice (not a whole view) does not carry -- each slice and the concatenated output are tagged again
-    mx = _x2() and H.mx_of(x)
     if N > max_n:
-        def part(t, i, j):
-            sl = t[i:j]
-            if mx and H.mx_of(t):
-                sl._mx = True
-            return sl
-
+        # the format of a carrier (layers/carrier.py) is known only through the tensor object's tag, which neither a batch
+        # slice (not a whole view) nor `cat` carries: each slice and the concatenated output are tagged like their source
+        part = lambda t, i, j: carrier.like(t, t[i:j])
         parts = []
         for i in range(0, N, max_n):
             j = min(N, i + max_n)
             parts.append(hip_conv(part(x, i, j), conv, relu=relu, residual=None if residual is None else part(residual, i, j),
                                   pool2=pool2, shortcut=None if shortcut is None else (part(shortcut[0], i, j), shortcut[1]),
                                   out_fp32=out_fp32))
-        out = torch.cat(parts)
-        if mx and not out_fp32:
-            out._mx = True
-        return out
+        return carrier.like(parts[0], torch.cat(parts))
     geom = dict(n_img=N, H=Hh, W=Ww, Cin=Cin, Ho=Ho, Wo=Wo, KH=k, KW=k, stride=s, pad=p, dil=d)
-    if mx:
+    if _x2() and H.mx_of(x):
         # "parity_mx": x (and residual / shortcut input) are unit-scale f16mx maps; fp16 hi*hi + block-scaled e4m3 cross terms
         # on the f16mx weights (per-row scales, encoded once: the stages are frozen or re-encoded per optimizer step); the
         # output is f16mx again, or real fp32 for the map that leaves the backbone
@@ -177,10 +168,7 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
             assert res2d is None or H.mx_of(residual)
             out = H.gemm_mx(x, None, wm, ws, conv=geom, bias=b, relu=relu, residual=res2d,
                             residual_fmt=H.MX if res2d is not None else None, out_dtype=fmt)
-        out = out.view(N, Ho, Wo, conv.out_channels)
-        if not out_fp32:
-            out._mx = True
-        return out
+        return out.view(N, Ho, Wo, conv.out_channels)  # (a whole view of what gemm_mx tagged)
     if _x2():
         # x (and residual / shortcut input) are bf16x2 maps; three-MFMA products on the bf16x2 weights; the output is
         # bf16x2 again, or real fp32 for the map that leaves the backbone (out_fp32)
@@ -441,12 +429,7 @@ def _masked(dy, y, cd):
     if y.dtype == torch.bfloat16 and dy.dtype != torch.bfloat16:
         dy = dy.to(torch.bfloat16)  # (the mask kernel takes dy in y's dtype; "bf16" precision: bf16 gradients anyway)
     return H.mask_transpose(dy.reshape(P, C), y.reshape(P, C), 1.0, cd, want_plain=True, want_t=False,
-                            y_x2=(y.dtype == torch.float32 and _is_x2_map(y, C)))[0]
-
-
-def _is_x2_map(t, channels):
-    """A bf16x2 carrier and a real fp32 map have the same dtype and shape; the blocks tag what they emit."""
-    return bool(getattr(t, "_x2_map", False))
+                            y_x2=carrier.fmt_of(y) == H.X2)[0]
 
 
 def _conv_dgrad(g2d, conv, N, Hh, Ww, cd):
@@ -467,7 +450,7 @@ def _conv_wgrad(g2d, xin, conv, cd):
     k = conv.kernel_size
     N, Hh, Ww, Ci = xin.shape
     P = N * Hh * Ww
-    x2 = _is_x2_map(xin, Ci)
+    x2 = carrier.fmt_of(xin) == H.X2  # (a bf16x2 carrier and a real fp32 map have the same dtype and shape: the tag tells)
     # patch rows are materialised in blocks of at most ~1 GiB (the stem's 64-channel convs at 32 images would be 8.8 GB at
     # once): the blocks' contributions accumulate into dW
     step = P if k == 1 else max(64, (WGRAD_PATCH_BYTES // (k * k * Ci * xin.element_size())) // 64 * 64)
@@ -497,13 +480,11 @@ def _block_forward_saving(block, x):
     """The block's forward on the HIP kernels (exactly BasicBlock.forward / BottleneckBlock.forward), keeping what the
     backward reads: -> (out, [inputs of conv1, conv2(, conv3)])."""
     last = getattr(block, "_emits_fp32", False) and not block.has_pool
-    tag = lambda t, real_fp32=False: (setattr(t, "_x2_map", _x2() and not real_fp32) or t)
-    tag(x)
-    h = tag(hip_conv(x, block.conv1, relu=True))
+    h = hip_conv(x, block.conv1, relu=True)
     ins = [x, h]
     tail = block.conv2
     if isinstance(block, BottleneckBlock):
-        h = tag(hip_conv(h, block.conv2, relu=True))
+        h = hip_conv(h, block.conv2, relu=True)
         ins.append(h)
         tail = block.conv3
     if _fusable_shortcut(block.shortcut, x) and h.shape[:3] == x.shape[:3] and \
@@ -512,11 +493,10 @@ def _block_forward_saving(block, x):
     else:
         sc = hip_conv(x, block.shortcut) if block.shortcut is not None else x
         out = hip_conv(h, tail, relu=True, residual=sc, out_fp32=last)
-    tag(out, real_fp32=last)
     if block.has_pool:
         # the map the tail pool reads (the forward's fused 64-channel conv + pool never writes it: same bits, gemm.hip) and
         # the pooled map the next block takes
-        return tag(block._pool(out)), ins, out
+        return block._pool(out), ins, out
     return out, ins, out
 
 
@@ -527,7 +507,7 @@ def _block_backward(block, ins, out, dy, cd, need_dx):
     grads = {}
     if block.has_pool:  # `out` is the map the tail pool read: route dy back through the pool first
         dy = H.maxpool2x2_nhwc_backward(out, dy.contiguous(), block.pool_stride, zero_pad_br=block.pool_stride == 1,
-                                        x2=_is_x2_map(out, out.shape[-1]))
+                                        x2=carrier.fmt_of(out) == H.X2)
     g = _masked(dy.contiguous(), out, cd)  # through the block's last ReLU: gradient of conv_tail(h) + shortcut(x)
     g_tail = g
     for i in range(len(convs) - 1, -1, -1):
@@ -620,13 +600,12 @@ class _TrainableStem(torch.autograd.Function):
         net, stem = ctx.net, ctx.net.stem
         mean, std = ctx.norm
         cd = torch.float32 if (ctx.x3 is False and net.compute_dtype == torch.float32) else torch.bfloat16
-        tag = lambda t, on: (setattr(t, "_x2_map", on) or t)
         with torch.no_grad():
             with H.x3_mode(ctx.x3):
                 x2 = _x2()
-                a1 = tag(net._stem_conv1(images_u8, sizes, mean, std), x2)
-                a2 = tag(hip_conv(a1, stem.conv2, relu=True), x2)
-                a3 = tag(hip_conv(a2, stem.conv3, relu=True), x2)  # (the forward pools in this conv's epilogue: same bits)
+                a1 = net._stem_conv1(images_u8, sizes, mean, std)  # (bf16x2 maps are tagged by the kernel fronts)
+                a2 = hip_conv(a1, stem.conv2, relu=True)
+                a3 = hip_conv(a2, stem.conv3, relu=True)  # (the forward pools in this conv's epilogue: same bits)
             grads = {}
             with H.x3_mode(False):
                 N, Hh, Ww, _ = a3.shape
@@ -657,7 +636,10 @@ def _stage_backward_hip(ctx, dy, x, params):
     blocks = list(stage.children())
     with torch.no_grad():
         with H.x3_mode(ctx.x3):  # the forward's own kernels again: bit-identical activations, hence the forward's own masks
-            acts, cur = [], x
+            # x came through ctx.saved_tensors, which does not promise to hand back the tagged object: its format is stated
+            # again from the mode.  Every other map of the stage is a fresh kernel output, tagged by its front; the real-fp32
+            # map that leaves the backbone is untagged by construction
+            acts, cur = [], (carrier.tag(x, H.X2) if _x2() else x)
             for b in blocks:
                 nxt, ins, out = _block_forward_saving(b, cur)
                 acts.append((ins, out))
@@ -792,7 +774,6 @@ class ResNet(nn.Module):
                 # the map that crosses from the bf16x2 layers to the f16mx ones (enough 256-row tiles: see _mx_from)
                 with torch.no_grad():
                     x = H.mx_from_x2(x)
-                    x._mx = True
             if torch.is_grad_enabled() and any(p.requires_grad for p in params):
                 _warn_trainable_stage_once(name)
                 x = _TrainableStage.apply(stage, H.x3_active(), x, *params)

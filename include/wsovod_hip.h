@@ -587,6 +587,23 @@ int wsovod_bf16x2_encode(const float* src, long long ld_src, int rows, int cols,
                          wsovod_stream_t stream);
 int wsovod_bf16x2_decode(const void* src, long long ld_src, int rows, int cols, float* dst, long long ld_dst,
                          wsovod_stream_t stream);
+/* "parity_mx_train" precision: the input gradient dX = dA W of a Linear layer (box_head.py:60-66, autograd's F.linear
+ * backward in fp32) as ONE bf16x2 contraction, wsovod_gemm_nt with dtype_in = WSOVOD_BF16X2 on the two operands below.
+ * wsovod_mask_bf16x2: the backward prologue of wsovod_mask_transpose_ex -- v = dy * [y > 0] * scale, dy fp32, y in y_dtype =
+ * WSOVOD_F32 / WSOVOD_BF16 / WSOVOD_BF16X2 (ldy in values) or NULL = no mask, colsum (may be NULL, zero-filled by the caller)
+ * += the fp32 column sums of v -- written as an interleaved bf16x2 matrix (M, Np): hi = bf16(v), lo = bf16(v - hi); Np = N
+ * rounded up to whole groups of 32, ld_x2 >= Np in values, the columns N .. Np - 1 are written as zeros.  dA_hi (may be NULL):
+ * the plain bf16 matrix of the hi values (M, N; row stride ld_hi), the operand of the weight gradient (wsovod_gemm_tn). */
+int wsovod_mask_bf16x2(const float* dy, long long lddy, const void* y, long long ldy, int y_dtype, int M, int N, float scale,
+                       void* dA_x2, long long ld_x2, void* dA_hi, long long ld_hi, float* colsum, wsovod_stream_t stream);
+/* The fp32 master weight W (N, K; row stride ld_src) -> its TRANSPOSE as a bf16x2 matrix (K, Np), Np = N rounded up to whole
+ * groups of 32, ld_dst >= Np in values: the bytes of wsovod_bf16x2_encode on W^T, the columns N .. Np - 1 zeros. */
+int wsovod_bf16x2_encode_t(const float* src, long long ld_src, int N, int K, void* dst, long long ld_dst,
+                           wsovod_stream_t stream);
+/* Unit-scale f16mx (rows, cols; cols a multiple of 32, ld_src in values) -> the fp32 values hi + ql 2^-11 it stands for:
+ * the saved input of an f16mx Linear layer (box_head.py:60-75) decoded for a weight gradient that keeps the hi/lo split. */
+int wsovod_f16mx_to_f32(const void* src, long long ld_src, int rows, int cols, float* dst, long long ld_dst,
+                        wsovod_stream_t stream);
 /* wsovod_stem_conv1 for the "parity" precision: w32x2 = the bf16x2 encoding of the folded (64, 32) fp32 weight, out =
  * (N, Ho, Wo, 64) bf16x2 NHWC; the normalised image is split into hi / lo in LDS and every product is the three-MFMA
  * sum w_hi*a_hi + w_lo*a_hi + w_hi*a_lo (resnet_wsl.py:375-383,410-413; rcnn_wsovod.py:321-328). */

@@ -57,6 +57,55 @@ __global__ __launch_bounds__(256) void x2_decode_kernel(const bf16_t* __restrict
   }
 }
 
+// dst (K, Np) bf16x2 = the transpose of the fp32 matrix src (N, K): a 64 x 64 tile through LDS, coalesced fp32 reads along K,
+// 16-byte hi / lo pieces along N on the way out; the columns N .. Np - 1 of dst (Np a multiple of 32) are written as zeros
+__global__ __launch_bounds__(256) void x2_encode_t_kernel(const float* __restrict__ src, long long ld_src, int N, int K, int Np,
+                                                          bf16_t* __restrict__ dst, long long ld_dst) {
+  __shared__ float tile[64][65];
+  const int tid = threadIdx.x;
+  const int n0 = blockIdx.y * 64, k0 = blockIdx.x * 64;
+  const bool al = ((ld_src & 3) == 0) && (((uintptr_t)src & 15) == 0);
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int row = (tid >> 3) + 32 * it, cg = (tid & 7) * 8;
+    const int n = n0 + row, k = k0 + cg;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (n < N && k < K) {
+      const float* s = src + (long long)n * ld_src + k;
+      if (al && k + 8 <= K) {
+        const f32x4 a = *(const f32x4*)s, b = *(const f32x4*)(s + 4);
+        v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (k + j < K) v[j] = s[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tile[row][cg + j] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int col = (tid >> 3) + 32 * it, rg = (tid & 7) * 8;
+    const int k = k0 + col, n = n0 + rg;
+    if (k < K && n < Np) {
+      bf16x8 hi, lo;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = tile[rg + j][col];
+        hi[j] = (bf16_t)v;
+        lo[j] = lo_of(v, hi[j]);
+      }
+      bf16_t* d = dst + 2 * (long long)k * ld_dst + ((n >> 5) << 6) + (n & 31);
+      *(bf16x8*)d = hi;
+      *(bf16x8*)(d + 32) = lo;
+    }
+  }
+}
+
 // 2x2 max pool, NHWC, C values per pixel (C % 32 == 0): the (hi, lo) pair of the largest hi + lo is copied
 __global__ void x2_maxpool2x2_kernel(const bf16_t* __restrict__ in, int N, int H, int W, int C, int Ho, int Wo, int stride,
                                      int zero_pad, bf16_t* __restrict__ out) {
@@ -178,6 +227,22 @@ int wsovod_bf16x2_encode(const float* src, long long ld_src, int rows, int cols,
   hipLaunchKernelGGL(x2_encode_kernel, dim3(grid_for((long long)rows * (cols / 8), 256)), dim3(256), 0, s, src, ld_src, rows,
                      cols, (bf16_t*)dst, ld_dst);
   WS_CHECK_LAUNCH("wsovod_bf16x2_encode");
+  return WSOVOD_OK;
+}
+
+int wsovod_bf16x2_encode_t(const float* src, long long ld_src, int N, int K, void* dst, long long ld_dst,
+                           wsovod_stream_t stream) {
+  WS_CHECK_ARG(N >= 0 && K >= 0, "wsovod_bf16x2_encode_t: negative dimension");
+  if (N == 0 || K == 0) return WSOVOD_OK;
+  const int Np = ceil_div(N, 32) * 32;
+  WS_CHECK_ARG(src && dst && ld_src >= K && ld_dst >= Np && ld_dst % 4 == 0 && ((uintptr_t)dst & 15) == 0,
+               "wsovod_bf16x2_encode_t: bad pointer / leading dimension (ld_dst >= N rounded up to 32, a multiple of 4)");
+  static int slot = wsovod::prof_slot("bf16x2_encode_t");
+  hipStream_t s = (hipStream_t)stream;
+  wsovod::ProfScope prof(slot, s, 0.0, (double)N * K * 8.0);
+  hipLaunchKernelGGL(x2_encode_t_kernel, dim3(ceil_div(K, 64), ceil_div(Np, 64)), dim3(256), 0, s, src, ld_src, N, K, Np,
+                     (bf16_t*)dst, ld_dst);
+  WS_CHECK_LAUNCH("wsovod_bf16x2_encode_t");
   return WSOVOD_OK;
 }
 

@@ -4,6 +4,7 @@
 // All are coalesced 16-B-per-lane streaming kernels; none is reshaped into a GEMM.
 #include "common.h"
 #include "f16mx.h"
+#include "gemm_common.h"
 #include <algorithm>
 #include <vector>
 
@@ -821,6 +822,92 @@ __global__ __launch_bounds__(256) void mask_transpose_kernel(const TI* __restric
   }
 }
 
+// The same prologue with the masked gradient written as an interleaved bf16x2 matrix (include/wsovod_hip.h:
+// wsovod_mask_bf16x2): v = dy * [y > 0] * scale, hi = bf16(v), lo = bf16(v - hi) in groups of [32 hi | 32 lo] -- the A operand
+// of the three-product input-gradient contraction, in ONE pass instead of an fp32 write plus a split pass.  A lane owns 8
+// consecutive values of a row = 16 B of hi and 16 B of lo half a line further; the columns N .. Np - 1 (Np = N rounded up to
+// 32) are written as zeros, so the carrier needs no fill.  dHi (optional): the hi values as a plain bf16 matrix (the weight
+// gradient's operand).  Column sums as in mask_transpose_kernel, from the fp32 values.
+template <typename TY, bool Y_X2>
+__global__ __launch_bounds__(256) void mask_x2_kernel(const float* __restrict__ dy, long long lddy, const TY* __restrict__ y,
+                                                      long long ldy, int M, int N, int Np, float scale,
+                                                      bf16_t* __restrict__ dX2, long long ldx, bf16_t* __restrict__ dHi,
+                                                      long long ldh, float* __restrict__ colsum,
+                                                      float* __restrict__ colpart) {
+  __shared__ float tile[64][65];
+  const int tid = threadIdx.x;
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  const bool dy_al = ((lddy * sizeof(float)) % 16 == 0) && (((uintptr_t)dy & 15) == 0);
+  const bool y_al = y && (Y_X2 || (ldy * sizeof(TY)) % 16 == 0) && (((uintptr_t)y & 15) == 0);
+  const bool hi_al = dHi && ((ldh * sizeof(bf16_t)) % 16 == 0) && (((uintptr_t)dHi & 15) == 0);
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int row = (tid >> 3) + 32 * it, cg = (tid & 7) * 8;
+    const int m = m0 + row, n = n0 + cg;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (m < M && n < N) {
+      const bool full = n + 8 <= N;
+      load8(dy + (long long)m * lddy + n, dy_al && full, N - n, v);
+      if (y) {
+        float yv[8];
+        if constexpr (Y_X2) load8(y + 2 * (long long)m * ldy + ((n >> 5) << 6) + (n & 31), y_al && full, N - n, yv);
+        else load8(y + (long long)m * ldy + n, y_al && full, N - n, yv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = yv[j] > 0.f ? v[j] * scale : 0.f;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] *= scale;
+      }
+      if (dHi) store8(dHi + (long long)m * ldh + n, hi_al && full, N - n, v);
+    }
+    if (m < M && n < Np) {  // (whole 8-value pieces: Np is a multiple of 32; values past N are zeros)
+      bf16x8 hi, lo;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        hi[j] = (bf16_t)v[j];
+        lo[j] = wsovod_gemm::x2_lo(v[j], hi[j]);  // (an infinite value keeps lo = 0, as every bf16x2 encoder here)
+      }
+      bf16_t* d = dX2 + 2 * (long long)m * ldx + ((n >> 5) << 6) + (n & 31);
+      *(bf16x8*)d = hi;
+      *(bf16x8*)(d + 32) = lo;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tile[row][cg + j] = v[j];
+  }
+  if (colsum) {
+    __shared__ float part[4][64];
+    __syncthreads();
+    const int col = tid & 63, q = tid >> 6;
+    float sacc = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sacc += tile[q * 16 + r][col];
+    part[q][col] = sacc;
+    __syncthreads();
+    if (q == 0 && n0 + col < N) {
+      const float t = (part[0][col] + part[1][col]) + (part[2][col] + part[3][col]);
+      if (colpart) colpart[(long long)blockIdx.y * N + n0 + col] = t;
+      else if (t != 0.f) atomicAdd(colsum + n0 + col, t);
+    }
+  }
+}
+
+// unit-scale f16mx -> fp32 (include/wsovod_hip.h: wsovod_f16mx_to_f32): one thread = 8 consecutive values of a row
+__global__ __launch_bounds__(256) void mx_to_f32_kernel(const char* __restrict__ src, long long ld_src_bytes, int rows, int cols,
+                                                        float* __restrict__ dst, long long ld_dst) {
+  const int cg = cols >> 3;
+  const long long total = (long long)rows * cg;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / cg), c = (int)(i - (long long)r * cg) * 8;
+    const char* row = src + (long long)r * ld_src_bytes;
+    const f32x4 a = wsovod_mx::mx_load4_unit(row, c), b = wsovod_mx::mx_load4_unit(row, c + 4);
+    float* d = dst + (long long)r * ld_dst + c;
+    *(f32x4*)d = a;
+    *(f32x4*)(d + 4) = b;
+  }
+}
+
 // out[m][n] = x[m][n] + add[row_group[m]][n]   (box_features += data_aware_features,
 // roi_heads.py:762-763; the per-proposal repeat of data_aware_features_head.py:117-121 is
 // never materialised)
@@ -972,6 +1059,48 @@ int wsovod_mask_transpose_ex(const void* dy, long long lddy, int dy_dtype, const
                              int N, float scale, void* dA, long long ldda, void* dAt, long long ldt, int out_dtype,
                              float* colsum, wsovod_stream_t stream) {
   return mask_transpose_impl(dy, lddy, y, ldy, dy_dtype, M, N, scale, dA, ldda, dAt, ldt, out_dtype, colsum, stream, y_dtype);
+}
+
+int wsovod_mask_bf16x2(const float* dy, long long lddy, const void* y, long long ldy, int y_dtype, int M, int N, float scale,
+                       void* dA_x2, long long ld_x2, void* dA_hi, long long ld_hi, float* colsum, wsovod_stream_t stream) {
+  WS_CHECK_ARG(M >= 0 && N >= 0, "wsovod_mask_bf16x2: negative dimension");
+  if (M == 0 || N == 0) return WSOVOD_OK;
+  const int Np = ceil_div(N, 32) * 32;
+  WS_CHECK_ARG(dy && dA_x2 && lddy >= N && ld_x2 >= Np && ld_x2 % 4 == 0 && ((uintptr_t)dA_x2 & 15) == 0,
+               "wsovod_mask_bf16x2: bad pointer / leading dimension (ld_x2 >= N rounded up to 32, a multiple of 4)");
+  WS_CHECK_ARG(!dA_hi || ld_hi >= N, "wsovod_mask_bf16x2: ld_hi=%lld < N", ld_hi);
+  WS_CHECK_ARG(!y || (y_dtype == WSOVOD_BF16X2 ? (N % 8 == 0 && ldy % 4 == 0 && ldy >= N && ((uintptr_t)y & 15) == 0)
+                                                : ((y_dtype == WSOVOD_F32 || y_dtype == WSOVOD_BF16) && ldy >= N)),
+               "wsovod_mask_bf16x2: y must be fp32, bf16 or bf16x2 (then N a multiple of 8, 16-byte aligned rows)");
+  static int slot = wsovod::prof_slot("mask_bf16x2");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(ceil_div(Np, 64), ceil_div(M, 64));
+  wsovod::ProfScope prof(slot, s, 0.0, (double)M * N * (4.0 + 2.0 + 4.0 + (dA_hi ? 2.0 : 0.0)));
+  float* colpart = colsum ? colpart_workspace((size_t)grid.y * N, s) : nullptr;
+#define MX2(TY, YX2) hipLaunchKernelGGL((mask_x2_kernel<TY, YX2>), grid, dim3(256), 0, s, dy, lddy, (const TY*)y, ldy, M, N, Np, scale, (bf16_t*)dA_x2, ld_x2, (bf16_t*)dA_hi, ld_hi, colsum, colpart)
+  if (y && y_dtype == WSOVOD_BF16X2) MX2(bf16_t, true);
+  else if (y && y_dtype == WSOVOD_BF16) MX2(bf16_t, false);
+  else MX2(float, false);
+#undef MX2
+  if (colpart) hipLaunchKernelGGL(colsum_rows_kernel, dim3(ceil_div(N, 32)), dim3(256), 0, s, colpart, (int)grid.y, N, colsum);
+  WS_CHECK_LAUNCH("wsovod_mask_bf16x2");
+  return WSOVOD_OK;
+}
+
+int wsovod_f16mx_to_f32(const void* src, long long ld_src, int rows, int cols, float* dst, long long ld_dst,
+                        wsovod_stream_t stream) {
+  WS_CHECK_ARG(rows >= 0 && cols >= 0 && cols % 32 == 0, "wsovod_f16mx_to_f32: cols=%d must be a multiple of 32", cols);
+  if (rows == 0 || cols == 0) return WSOVOD_OK;
+  WS_CHECK_ARG(src && dst && ld_src >= cols && ld_src % 4 == 0 && ld_dst >= cols && ld_dst % 4 == 0 &&
+                   (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
+               "wsovod_f16mx_to_f32: bad pointer / leading dimension");
+  static int slot = wsovod::prof_slot("f16mx_to_f32");
+  hipStream_t s = (hipStream_t)stream;
+  wsovod::ProfScope prof(slot, s, 0.0, (double)rows * cols * 8.0);
+  hipLaunchKernelGGL(mx_to_f32_kernel, dim3(grid_for((long long)rows * (cols / 8), 256)), dim3(256), 0, s, (const char*)src,
+                     ld_src * 4, rows, cols, dst, ld_dst);
+  WS_CHECK_LAUNCH("wsovod_f16mx_to_f32");
+  return WSOVOD_OK;
 }
 
 int wsovod_add_group_rows(const void* x, long long ldx, int dtype, const int* row_group, const float* add,

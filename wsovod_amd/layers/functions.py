@@ -11,6 +11,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from . import carrier
 from . import hip_ops as H
 from . import operand_cache
 
@@ -85,6 +86,13 @@ def _bwd_split():
     return frozenset(w for w in which.split(",") if w in ("dw", "dx"))
 
 
+def _pt_dx():
+    """WSOVOD_PT_DX: how a split input gradient dX = dA W is contracted under "parity_mx_train" -- "x2" (default): ONE bf16x2
+    contraction on a masked gradient written as bf16x2 in one pass and the cached bf16x2 encoding of W^T; "x3": the
+    generic route of "parity_train" (fp32 dA, a split pass, the fp32 master transposed and split at every step)."""
+    return "x3" if os.environ.get("WSOVOD_PT_DX", "x2") == "x3" else "x2"
+
+
 def _no_split(x3):
     """The x3 state a backward pass runs under: the forward-only modes ("fwd", "x2") contract in plain bf16."""
     return x3 if x3 not in ("fwd", "x2") else False
@@ -128,8 +136,10 @@ class _Linear(Function):
                           out_dtype=out_dtype)
         ctx.relu, ctx.dropout_p = relu, dropout_p
         ctx.bwd = _bwd_split() if ctx.x2 else frozenset()
-        if ctx.bwd and H.mx_of(x):
-            raise NotImplementedError('"parity_train" (a backward that keeps the hi/lo split) is not combined with f16mx activations')
+        # "parity_mx_train" (the f16mx forward of "parity_mx" + a backward split): the layer's input may be an f16mx carrier
+        # (saved tensors lose their tag: recorded here), and the backward takes the mode's own routes (_backward)
+        ctx.mx_in = bool(ctx.x2 and H.mx_of(x))
+        ctx.mx_mode = bool(ctx.x2 and H.mx_active())
         if "dw" in ctx.bwd:
             x_hi = None  # the split weight gradient reads hi AND lo: the carrier itself is kept (either layout)
         if y_mask is not None:
@@ -154,28 +164,50 @@ class _Linear(Function):
     def _backward_split(ctx, dy):
         """"parity_train": dW = dA^T X and / or dX = dA W with the hi/lo split kept -- fp32 dA (mask applied, not rounded),
         the saved bf16x2 input decoded to fp32, the fp32 master weight; the contractions are the "bf16x3" mode's (three bf16
-        MFMA products per value pair, operands split on the fly).  A contraction not named in ctx.bwd runs as in "parity"."""
+        MFMA products per value pair, operands split on the fly).  A contraction not named in ctx.bwd runs as in "parity".
+
+        Which function and which route a layer takes (split = WSOVOD_PT_SPLIT restricted to the gradients the layer has to
+        produce; PT_DX = WSOVOD_PT_DX; "x2 route" = mask_x2 + _dx_x2, "x3 route" = fp32 dA + x3_mode("full")):
+
+            mode              split      PT_DX   function          dW                        dX
+            parity_train      any        -       _backward_split   x3 if "dw" else bf16      x3 if "dx" else bf16
+            parity_mx_train   {}         any     _backward         bf16 (fused update kept)  bf16 (if wanted at all)
+            parity_mx_train   {dx}       x2      _backward         bf16 (fused update kept)  x2 route
+            parity_mx_train   {dx}       x3      _backward_split   bf16                      x3 route
+            parity_mx_train   {dw}       any     _backward_split   x3 (f16mx x decoded)      bf16 (if wanted)
+            parity_mx_train   {dw,dx}    x2      _backward_split   x3 (f16mx x decoded)      x2 route (dy is masked twice)
+            parity_mx_train   {dw,dx}    x3      _backward_split   x3 (f16mx x decoded)      x3 route
+
+        So `dx_x2` below is reached only with "dw" in the split; the column sum goes to exactly one of the masking passes."""
         x, weight, y = ctx.saved_tensors
         M, K = x.shape
         N = weight.size(0)
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
         s_dw, s_dx = need_dw and "dw" in ctx.bwd, need_dx and "dx" in ctx.bwd
+        dx_x2 = s_dx and ctx.mx_mode and _pt_dx() == "x2"  # "parity_mx_train": dX as ONE bf16x2 contraction (_dx_x2)
         dy = _contig2d(dy)
         scale = 1.0 / (1.0 - ctx.dropout_p) if ctx.dropout_p > 0 else 1.0
         Mp, Np = _pad(M, 64), _pad(N, 8)
         y_x2 = ctx.y_x2
         db = torch.zeros((N,), dtype=torch.float32, device=dy.device) if need_db else None
         dA32 = dAt32 = dA16 = None
-        if s_dw or s_dx:
-            dA32, dAt32 = H.mask_transpose(dy, y, scale, torch.float32, want_plain=s_dx, want_t=s_dw, ld_t=Mp, ld_plain=Np,
-                                           colsum=db, y_x2=y_x2)
-        if (need_dw and not s_dw) or (need_dx and not s_dx) or (db is not None and dA32 is None and dAt32 is None):
+        dAx2 = None
+        if s_dw or (s_dx and not dx_x2):
+            dA32, dAt32 = H.mask_transpose(dy, y, scale, torch.float32, want_plain=s_dx and not dx_x2, want_t=s_dw, ld_t=Mp,
+                                           ld_plain=Np, colsum=db, y_x2=y_x2)
+        if dx_x2:
+            dAx2, _ = H.mask_x2(dy, y, scale, colsum=db if dAt32 is None else None, y_x2=y_x2)
+        if (need_dw and not s_dw) or (need_dx and not s_dx) or (db is not None and dA32 is None and dAt32 is None
+                                                                  and dAx2 is None):
             dA16, _ = H.mask_transpose(dy, y, scale, torch.bfloat16, want_plain=True, want_t=False, ld_plain=Np,
                                        colsum=db if (dA32 is None and dAt32 is None) else None, y_x2=y_x2)
         dx = dw = None
         if s_dw:
-            xt = H.transpose_cast(H.x2_to_f32(x), torch.float32, ld_dst=Mp)  # (K, Mp)
+            # (the saved carrier decoded on the device: bf16x2 in either layout, or -- "parity_mx_train" -- unit-scale f16mx)
+            x32 = H.f16mx_to_f32(carrier.tag(x, carrier.MX)) if ctx.mx_in else H.x2_to_f32(x)
+            xt = H.transpose_cast(x32, torch.float32, ld_dst=Mp)  # (K, Mp)
+            del x32
             with H.x3_mode("full"):
                 dw = H.gemm_nt(dAt32, xt, out_dtype=torch.float32)  # (N, K)
             del xt
@@ -186,7 +218,9 @@ class _Linear(Function):
                 dw = dw[:N]
         if dw is not None and ctx.dw_split is not None and 0 < ctx.dw_split[0] < N and ctx.dw_split[0] % 8 == 0:
             ctx.dw_split[1](dw[:ctx.dw_split[0]])  # (a data-parallel trainer's early block: handed over late, still first)
-        if s_dx:
+        if dx_x2:
+            dx = _Linear._dx_x2(dAx2, weight)
+        elif s_dx:
             wt = H.transpose_cast(weight, torch.float32, ld_dst=Np)  # (K, Np)
             with H.x3_mode("full"):
                 dx = H.gemm_nt(dA32, wt, out_dtype=torch.float32)  # (M, K)
@@ -195,9 +229,24 @@ class _Linear(Function):
         return dx, dw, db, None, None, None, None, None, None
 
     @staticmethod
+    def _dx_x2(dAx2, weight):
+        """dX = dA W with the hi/lo split kept on BOTH operands, as one contraction of the lean bf16x2 tile: dA as mask_x2
+        wrote it, W^T as the cached bf16x2 encoding of the fp32 master (K, Np) -- dA_hi W_hi + dA_hi W_lo + dA_lo W_hi."""
+        return H.gemm_nt(dAx2, H.x2t_cached(weight), x2=True, out_dtype=torch.float32)
+
+    @staticmethod
     def _backward(ctx, dy):
+        dx_x2 = False
         if ctx.bwd:
-            return _Linear._backward_split(ctx, dy)
+            # "parity_mx_train": which of the contractions this layer has to run keep the split?  None (fc1 under "dx": the
+            # pooled tensor takes no gradient) -> the ordinary backward below, with its fused dW + optimizer kernel and the
+            # data-parallel early block, exactly as under "parity_mx".  Only dX, on the bf16x2 route -> the ordinary backward
+            # too, with that ONE contraction replaced.  Everything else ("dw", WSOVOD_PT_DX=x3; always under "parity_train",
+            # whose bits stay as they are) is _backward_split.
+            split = ctx.bwd & {w for w, need in (("dx", ctx.needs_input_grad[0]), ("dw", ctx.needs_input_grad[1])) if need}
+            if not ctx.mx_mode or "dw" in split or (split and _pt_dx() != "x2"):
+                return _Linear._backward_split(ctx, dy)
+            dx_x2 = bool(split)
         x, weight, y = ctx.saved_tensors
         in_dtype = torch.float32 if ctx.x_is_hi else x.dtype
         if ctx.x3 == "fwd":  # bf16x3f: plain bf16 backward on a cast of the saved fp32 input
@@ -216,8 +265,14 @@ class _Linear(Function):
         tn = ctx.x2 or (_USE_TN and need_dw and cd == torch.bfloat16 and K % 8 == 0 and x.stride(1) == 1
                         and x.stride(0) % 8 == 0 and ((Np + 255) // 256) * ((K + 255) // 256) >= 128)
         db = torch.zeros((N,), dtype=torch.float32, device=dy.device) if need_db else None  # summed in the same pass
-        dA, dAt = H.mask_transpose(dy, y, scale, cd, want_plain=need_dx or tn, want_t=need_dw and not tn,
-                                   ld_t=Mp, ld_plain=Np, colsum=db, y_x2=ctx.x2 and ctx.y_x2)
+        if dx_x2:
+            # one pass: the bf16x2 masked gradient for dX and, for dW, its hi values as the plain bf16 matrix that
+            # mask_transpose writes under "parity_mx" (the same rounding of the same fp32 values: dW keeps its bits)
+            dAx2, dA = H.mask_x2(dy, y, scale, colsum=db, y_x2=ctx.y_x2, want_hi=need_dw, ld_hi=Np)
+            dAt = None
+        else:
+            dA, dAt = H.mask_transpose(dy, y, scale, cd, want_plain=need_dx or tn, want_t=need_dw and not tn,
+                                       ld_t=Mp, ld_plain=Np, colsum=db, y_x2=ctx.x2 and ctx.y_x2)
         dx = dw = None
         # round 6: the trainer may have put a fused update on ONE large weight (engine/trainer.py:_FusedUpdate): dW and the
         # optimizer step of that tensor are then one kernel and no gradient is returned (the optimizer skips `grad is None`).
@@ -225,7 +280,8 @@ class _Linear(Function):
         fused = getattr(weight, "_fused_update", None) if (tn and need_dw and Np == N and ctx.dw_split is None) else None
         if fused is not None and fused.wants(M):
             if need_dx:
-                dx = H.gemm_nt(dA, H.transpose_cast(weight, cd, ld_dst=Np), out_dtype=in_dtype)
+                dx = _Linear._dx_x2(dAx2, weight) if dx_x2 else \
+                    H.gemm_nt(dA, H.transpose_cast(weight, cd, ld_dst=Np), out_dtype=in_dtype)
             if fused(dA, x, q_x2):
                 return dx, None, db, None, None, None, None, None, None
             need_dx = need_dx and dx is None
@@ -244,7 +300,9 @@ class _Linear(Function):
         elif need_dw:
             xt = H.transpose_cast(x, cd, ld_dst=Mp)  # (K, Mp)
             dw = H.gemm_nt(dAt, xt, out_dtype=torch.float32)  # (N,K) = dA^T X, reduction over proposals
-        if need_dx and dx is None:
+        if need_dx and dx is None and dx_x2:
+            dx = _Linear._dx_x2(dAx2, weight)
+        elif need_dx and dx is None:
             wt = H.transpose_cast(weight, cd, ld_dst=Np)  # (K, Np) shadow of W^T
             dx = H.gemm_nt(dA, wt, out_dtype=in_dtype)  # (M,K)
         return dx, dw, db, None, None, None, None, None, None
@@ -276,6 +334,9 @@ class _LinearGroup(Function):
         for h in heads:
             first.append(first[-1] + h[2])
         ctx.x2 = _x2_mode()
+        # (under "parity_mx" / "parity_mx_train" the LAST FC layer of the box head hands bf16x2 to the heads at every row
+        # count -- box_head.py -- so no f16mx carrier reaches the group, and its backward split stays the bf16x2 one)
+        carrier.refuse("linear_group", (x,), reads=(carrier.X2P,))  # (a planar carrier: gemm_nt's own refusal, as before)
 
         def operand(w):
             return H.x2_cached(w) if ctx.x2 else weight_shadow(w, cd)

@@ -432,6 +432,24 @@ def mx_to_f32(carrier):
     return hi + ql
 
 
+def f16mx_to_f32(x):
+    """The fp32 values hi + ql 2^-11 of a unit-scale f16mx carrier, decoded on the device (wsovod_f16mx_to_f32): the saved
+    input of an f16mx Linear layer for a weight gradient that keeps the hi/lo split.  Only a tensor RECORDED as f16mx is
+    taken (a saved tensor is re-tagged by its Function, which knows what it saved); `mx_to_f32` is the torch composition the
+    kernel is tested against."""
+    require_gpu(x)
+    carrier.refuse("f16mx_to_f32", (x,), reads=(MX,))
+    if carrier.fmt_of(x) != MX:
+        raise RuntimeError("wsovod_hip f16mx_to_f32: got a tensor that is not recorded as an f16mx carrier")
+    src = x.reshape(x.shape[0], -1)  # (groups of 32 run along the flattened row)
+    if src.stride(1) != 1 or src.shape[1] % 32:
+        raise RuntimeError("wsovod_hip f16mx_to_f32: rows of whole 32-value groups with a contiguous last dim expected")
+    rows, cols = src.shape
+    out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
+    check(lib().wsovod_f16mx_to_f32(ptr(src), src.stride(0), rows, cols, ptr(out), out.stride(0), stream()), "f16mx_to_f32")
+    return out.view(x.shape)
+
+
 def mx_from_x2(src):
     """interleaved bf16x2 tensor -> unit-scale f16mx tensor of the same shape (wsovod_f16mx_from_bf16x2)."""
     require_gpu(src)
@@ -536,6 +554,26 @@ def x2_cached(t, view_rows_cols=None):
     """bf16x2 encoding of a weight, cached on the tensor object and keyed by its version counter (one re-encode per
     optimizer step at most; frozen backbone weights once)."""
     return operand_cache.lookup(t, "x2", x2_encode, view_rows_cols)
+
+
+def x2_encode_t(src):
+    """fp32 (N, K) with a contiguous last dim -> the bf16x2 encoding of its TRANSPOSE, (K, Np) with Np = N rounded up to 32:
+    the bytes of x2_encode(src.t().contiguous()), zeros in the columns N .. Np - 1 (wsovod_bf16x2_encode_t)."""
+    require_gpu(src)
+    carrier.refuse("x2_encode_t", (src,))
+    if src.dtype != torch.float32 or src.dim() != 2 or src.stride(1) != 1:
+        raise RuntimeError("x2_encode_t: source must be a 2-D fp32 matrix with a contiguous last dim")
+    N, K = src.shape
+    out = torch.empty((K, (N + 31) // 32 * 32), dtype=torch.float32, device=src.device)
+    check(lib().wsovod_bf16x2_encode_t(ptr(src), src.stride(0), N, K, ptr(out), out.stride(0), stream()), "bf16x2_encode_t")
+    return carrier.tag(out, X2)
+
+
+def x2t_cached(t):
+    """bf16x2 encoding of a weight's transpose (x2_encode_t): the B operand of the "parity_mx_train" input gradient dX = dA W,
+    cached on the tensor object under a format of its own ("x2t") and keyed by its version counter.  No update kernel
+    refreshes it: it is read BEFORE the step's update and goes stale with it, one encode per optimizer step."""
+    return operand_cache.lookup(t, "x2t", x2_encode_t)
 
 
 def stem_conv1_x2(images_u8, sizes, mean, std, w32_x2, bias):
@@ -1135,6 +1173,30 @@ def mask_transpose(dy, y, scale, out_dtype, want_plain=True, want_t=True, ld_t=N
                                       M, N, C.c_float(scale), ptr(dA), ldp, ptr(dAt), _ld(dAt) if want_t else 0,
                                       dtype_code(out_dtype), stream()), "mask_transpose")
     return dA, dAt
+
+
+def mask_x2(dy, y, scale, colsum=None, y_x2=False, want_hi=False, ld_hi=None):
+    """dA = dy * [y>0] * scale as an interleaved bf16x2 carrier (M, Np), Np = N rounded up to 32, padding columns zero: the A
+    operand of gemm_nt(x2=True) in ONE pass over dy (wsovod_mask_bf16x2; mask_transpose to fp32 + a split pass otherwise).
+    y: the layer's output in fp32 / bf16, or its bf16x2 carrier (y_x2), or None.  colsum as in mask_transpose.
+    want_hi: also the plain bf16 matrix (M, ld_hi>=N) of the hi values, zero padded.  -> (carrier tagged X2, hi or None)."""
+    require_gpu(dy, y, colsum)
+    carrier.refuse("mask_x2", (dy, y))
+    if dy.dtype != torch.float32 or dy.dim() != 2:
+        raise RuntimeError("wsovod_hip mask_x2: the gradient must be a 2-D fp32 matrix")
+    M, N = dy.shape
+    out = torch.empty((M, (N + 31) // 32 * 32), dtype=torch.float32, device=dy.device)
+    hi = None
+    if want_hi:
+        ldh = ld_hi or N
+        hi = (torch.zeros if ldh != N else torch.empty)((M, ldh), dtype=torch.bfloat16, device=dy.device)
+    if colsum is not None:
+        assert colsum.dtype == torch.float32 and colsum.numel() == N and colsum.is_contiguous()
+    y_code = F32 if y is None else BF16X2 if y_x2 else dtype_code(y.dtype)
+    check(lib().wsovod_mask_bf16x2(ptr(dy), _ld(dy), ptr(y), _ld(y) if y is not None else 0, y_code, M, N, C.c_float(scale),
+                                   ptr(out), out.stride(0), ptr(hi), hi.stride(0) if hi is not None else 0, ptr(colsum),
+                                   stream()), "mask_bf16x2")
+    return carrier.tag(out, X2), hi
 
 
 def add_group_rows(x, row_group, add, x2=False):

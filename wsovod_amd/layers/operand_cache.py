@@ -4,14 +4,17 @@
     x2     bf16x2 encoding (hip_ops.x2_cached)
     mx     f16mx (carrier, scales) (hip_ops.mx_cached), with the per-tensor scale byte of a trained weight
     x3     three-way bf16 split (hip_ops._split3_cached)
+    x2t    bf16x2 encoding of the TRANSPOSE (hip_ops.x2t_cached): the "parity_mx_train" input gradient's B operand
 
 An entry is (key, operand) with key = (version, data_ptr, view_rows_cols, variant); variant is the operand side of an x3
 split, the dtype of a bf16 copy, else None.  Any in-place change of the tensor moves its version and the entry misses.
 
 The update kernels write a parameter through raw pointers and refresh ONE of its operands in the same pass.  Python then
 has to advance the version and re-stamp that entry: `refreshable` names the operand to hand to the kernel, `wrote` does the
-bookkeeping after an eager launch, `replayed` after the replay of a captured step (no Python ran).  Pure torch: the
-encoders stay with their kernels and are passed in.
+bookkeeping after an eager launch, `replayed` after the replay of a captured step (no Python ran).  An operand that no
+update kernel refreshes (x3, x2t) holds the values from BEFORE the update: it is never re-stamped, `wrote` and `replayed`
+leave it to miss by version (x2t is also dropped there -- a whole weight's worth of bytes that nothing can read again).
+Pure torch: the encoders stay with their kernels and are passed in.
 """
 import torch
 
@@ -21,10 +24,10 @@ _bump = torch.autograd.graph.increment_version
 
 
 class _Operands:
-    __slots__ = ("bf16", "x2", "mx", "x3", "mx_one_scale", "mx_byte")
+    __slots__ = ("bf16", "x2", "mx", "x3", "x2t", "mx_one_scale", "mx_byte")
 
     def __init__(self):
-        self.bf16 = self.x2 = self.mx = self.x3 = self.mx_byte = None
+        self.bf16 = self.x2 = self.mx = self.x3 = self.x2t = self.mx_byte = None
         self.mx_one_scale = False  # the mx entry was encoded with ONE scale for the tensor (mx_byte): refreshable
 
 
@@ -128,8 +131,10 @@ def wrote(p, fmt):
     """An update kernel wrote `p` through raw pointers and refreshed its `fmt` operand (as named by `refreshable`; None:
     none): the version advances, so that everything keyed on it is rebuilt, and that one entry is re-stamped."""
     _bump(p)
+    c = getattr(p, _ATTR, None)
+    if c is not None:
+        c.x2t = None
     if fmt is not None:
-        c = getattr(p, _ATTR)
         setattr(c, fmt, ((p._version, p.data_ptr(), None, _BF16 if fmt == "bf16" else None), getattr(c, fmt)[1]))
 
 
@@ -142,6 +147,7 @@ def replayed(p):
         return
     mx, x2, bf, ptr = _refreshable(p, c)
     _bump(p)
+    c.x2t = None  # (encoded inside the graph from the weights before the update: stale, as after an eager step)
     if mx is not None:
         c.mx = ((p._version, ptr, None, None), mx[1])
     if x2 is not None:

@@ -388,8 +388,9 @@ def _torch_block(block, x):
 def forward_precision(name):
     """MODEL.HIP.PRECISION "parity_train" = the "parity" forward (bf16x2 activations, three products) + a backward that
     keeps the split too (layers/functions.py:backward_split): every module sees "parity", the meta-arch sets the flag.
-    "parity_mx" likewise: the parity forward with its big contractions on the f16mx kernels (hip_ops.mx_mode)."""
-    return "parity" if name in ("parity_train", "parity_mx") else name
+    "parity_mx" likewise: the parity forward with its big contractions on the f16mx kernels (hip_ops.mx_mode), and
+    "parity_mx_train" = that forward + the backward split (both flags)."""
+    return "parity" if name in ("parity_train", "parity_mx", "parity_mx_train") else name
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -69,10 +69,11 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         self.logger = logging.getLogger(__name__)
         self.classifier = None
         # MODEL.HIP.PRECISION = "parity_train": the heads' backward keeps the hi/lo split (layers/functions.py)
-        self.backward_split = bool(cfg is not None and cfg.MODEL.HIP.PRECISION == "parity_train")
+        self.backward_split = bool(cfg is not None and cfg.MODEL.HIP.PRECISION in ("parity_train", "parity_mx_train"))
         # "parity_mx" (round 6): the parity forward with the res4 / res5 convs and the box head's FC layers on the block-scaled
         # f16mx kernels (layers/hip_ops.py:mx_mode); every module sees "parity", this flag selects the kernels
-        self.mx = bool(cfg is not None and cfg.MODEL.HIP.PRECISION == "parity_mx")
+        # "parity_mx_train": both flags -- the f16mx forward, and input-gradient contractions that keep the hi/lo split
+        self.mx = bool(cfg is not None and cfg.MODEL.HIP.PRECISION in ("parity_mx", "parity_mx_train"))
 
     @classmethod
     def from_config(cls, cfg):
@@ -197,6 +198,11 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
     def forward_trainable(self, st):
         from ..layers.functions import backward_split
 
+        if self.backward_split and getattr(self, "mx", False) and getattr(self.backbone, "has_trainable_stage", False):
+            raise NotImplementedError(
+                'MODEL.HIP.PRECISION "parity_mx_train" needs a frozen backbone (MODEL.BACKBONE.FREEZE_AT = 5, as in every '
+                "shipped WSR config): its split input gradients stop at the pooled tensor, and a trainable stage would "
+                'continue them through convolution backwards that keep no hi/lo split -- use "parity_train" or "parity_mx"')
         with H.x3_mode(self.x3), backward_split(self.backward_split), H.mx_mode(getattr(self, "mx", False)):
             return self._forward_trainable(st)
 

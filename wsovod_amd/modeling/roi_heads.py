@@ -24,6 +24,7 @@ from ..config import ROI_HEADS_REGISTRY, configurable
 from ..layers import functions as Fn
 from ..layers import hip_ops as H
 from ..structures import Boxes, ImageList, Instances, ShapeSpec
+from .backbone import forward_precision
 from .box_head import build_box_head
 from .class_heads import OpenVocabularyClassifier
 from .fast_rcnn_open_vocabulary import (InstanceRefinementOutputLayers, ObjectMiningOutputLayers,
@@ -222,7 +223,7 @@ class WSOVODROIHeads(ROIHeads):
             "positive_sample_fractions": cfg.WSOVOD.SAMPLING.POSITIVE_FRACTION,
             "cls_agnostic_bbox_known": cfg.WSOVOD.CLS_AGNOSTIC_BBOX_KNOWN, "pooler_type": pooler_type,
             "rpn_on": cfg.MODEL.PROPOSAL_GENERATOR.NAME != "PrecomputedProposals", "metadata": None,
-            "precision": "parity" if cfg.MODEL.HIP.PRECISION in ("parity_train", "parity_mx") else cfg.MODEL.HIP.PRECISION,
+            "precision": forward_precision(cfg.MODEL.HIP.PRECISION),
         }
 
     # ------------------------------------------------------------------------------

@@ -604,6 +604,14 @@ int wsovod_bf16x2_encode_t(const float* src, long long ld_src, int N, int K, voi
  * the saved input of an f16mx Linear layer (box_head.py:60-75) decoded for a weight gradient that keeps the hi/lo split. */
 int wsovod_f16mx_to_f32(const void* src, long long ld_src, int rows, int cols, float* dst, long long ld_dst,
                         wsovod_stream_t stream);
+/* Range audit of an f16mx matrix (rows, cols; cols a multiple of 32, row stride ld >= cols in values) by its bytes alone, at
+ * any scale: unit-scale activations and scaled weight operands alike.  The f16mx layers stand for box_head.py:60-75 and
+ * resnet_wsl.py:94-110, which compute in fp32 and know no range limit; the format's fp16 hi plane overflows beyond 65504 and its
+ * e4m3 q plane is clamped at 448 (times the scale), and nothing else reports either.  ACCUMULATES into four int64 DEVICE
+ * counters:  [0] += values audited;  [1] += values whose hi is not finite (exponent field all ones);  [2] += values whose q byte
+ * is at or above the format's top code, (b & 0x7f) >= 0x7e: |x 2^-s| rounded to 448 or was clamped there (from 432 up);
+ * [3] = max([3], bit pattern of the largest finite |hi|).  rows == 0 is a no-op.  The ql plane is not read. */
+int wsovod_f16mx_range(const void* src, long long ld, int rows, int cols, long long* counters, wsovod_stream_t stream);
 /* wsovod_stem_conv1 for the "parity" precision: w32x2 = the bf16x2 encoding of the folded (64, 32) fp32 weight, out =
  * (N, Ho, Wo, 64) bf16x2 NHWC; the normalised image is split into hi / lo in LDS and every product is the three-MFMA
  * sum w_hi*a_hi + w_lo*a_hi + w_hi*a_lo (resnet_wsl.py:375-383,410-413; rcnn_wsovod.py:321-328). */

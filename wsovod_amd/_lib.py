@@ -122,6 +122,7 @@ SIGNATURES = {
     "wsovod_mask_bf16x2": [_P, _L, _P, _L, _I, _I, _I, _F, _P, _L, _P, _L, _P, _P],
     "wsovod_bf16x2_encode_t": [_P, _L, _I, _I, _P, _L, _P],
     "wsovod_f16mx_to_f32": [_P, _L, _I, _I, _P, _L, _P],
+    "wsovod_f16mx_range": [_P, _L, _I, _I, _P, _P],
     "wsovod_stem_conv1_x2": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "wsovod_nms_segments": [_P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P],
     "wsovod_rpn_label_anchors": [_P, _I, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P],

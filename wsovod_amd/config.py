@@ -241,6 +241,10 @@ def add_wsovod_config(cfg):
     # bf16 backward: fp32-grade logits, bf16-grade gradients) | "parity" (the fast tolerance-meeting mode: the forward
     # split of "bf16x3f" on the activation format / kernels built for it -- DESIGN.md section 3)
     _C.MODEL.HIP.PRECISION = "bf16"
+    # range guard of the unscaled f16mx operands ("parity_mx" / "parity_mx_train" only; layers/mx_guard.py):
+    # "off" | "warn" | "raise" | "fallback" (to the bf16x2 kernels of "parity"); in training every PERIOD-th step is audited
+    _C.MODEL.HIP.MX_RANGE_GUARD = "off"
+    _C.MODEL.HIP.MX_RANGE_GUARD_PERIOD = 100
     return _C
 
 

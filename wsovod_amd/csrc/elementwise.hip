@@ -908,6 +908,70 @@ __global__ __launch_bounds__(256) void mx_to_f32_kernel(const char* __restrict__
   }
 }
 
+// range audit of an f16mx matrix by its bytes (include/wsovod_hip.h: wsovod_f16mx_range).  A lane owns one 16-byte chunk per
+// step and its position in the 128-byte group fixes what the chunk is (csrc/f16mx.h: mx_range_role_of); chunks per row and the
+// grid stride are multiples of 8, so the role never changes along the loop.  Four loads in flight per lane; the ql quarter is
+// not loaded.  counters: [0] += values, [1] += non-finite hi, [2] += q at the top code, [3] = max(largest finite |hi| bits).
+__global__ __launch_bounds__(256) void mx_range_kernel(const char* __restrict__ src, long long ld_bytes, int rows, int cols,
+                                                       unsigned long long* __restrict__ counters) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  const int cpr = cols >> 2;  // 16-byte chunks of a row
+  const long long total = (long long)rows * cpr;
+  const bool dense = ld_bytes == (long long)cols * 4;
+  const int chunk = threadIdx.x & 7;
+  const wsovod_mx::mx_range_role role = wsovod_mx::mx_range_role_of(chunk);
+  const bool loads = chunk < 6;
+  int flagged = 0, seen = 0;
+  wsovod_mx::s16x2 top = {wsovod_mx::kMxRangeMaxBias, wsovod_mx::kMxRangeMaxBias};
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i0 = (long long)blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += 4 * stride) {
+    u32x4 w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = i0 + u * stride;
+      w[u] = u32x4{0u, 0u, 0u, 0u};
+      if (i < total) {
+        ++seen;
+        if (loads) {
+          const long long off = dense ? i * 16 : (i / cpr) * ld_bytes + (i % cpr) * 16;
+          w[u] = *(const u32x4*)(src + off);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wsovod_mx::mx_range_word(w[u][j], role, flagged, top);
+  }
+  // lane -> wavefront -> workgroup, then at most one atomic per counter (none for a zero contribution)
+  int v[4] = {chunk < 4 ? seen * 8 : 0, chunk < 4 ? flagged : 0, (chunk == 4 || chunk == 5) ? flagged : 0,
+              chunk < 4 ? (int)(top[0] > top[1] ? top[0] : top[1]) - wsovod_mx::kMxRangeMaxBias : 0};
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] += __shfl_xor(v[k], m);
+    const int o = __shfl_xor(v[3], m);
+    v[3] = o > v[3] ? o : v[3];
+  }
+  __shared__ int part[4][4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 4; ++k) part[wave][k] = v[k];
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    if (k < 3) {
+      const unsigned long long t = (unsigned long long)part[0][k] + (unsigned long long)part[1][k] +
+                                   (unsigned long long)part[2][k] + (unsigned long long)part[3][k];
+      if (t) atomicAdd(counters + k, t);
+    } else {
+      const int a = part[0][3] > part[1][3] ? part[0][3] : part[1][3], b = part[2][3] > part[3][3] ? part[2][3] : part[3][3];
+      const int t = a > b ? a : b;
+      if (t) atomicMax(counters + 3, (unsigned long long)t);
+    }
+  }
+}
+
 // out[m][n] = x[m][n] + add[row_group[m]][n]   (box_features += data_aware_features,
 // roi_heads.py:762-763; the per-proposal repeat of data_aware_features_head.py:117-121 is
 // never materialised)
@@ -1100,6 +1164,24 @@ int wsovod_f16mx_to_f32(const void* src, long long ld_src, int rows, int cols, f
   hipLaunchKernelGGL(mx_to_f32_kernel, dim3(grid_for((long long)rows * (cols / 8), 256)), dim3(256), 0, s, (const char*)src,
                      ld_src * 4, rows, cols, dst, ld_dst);
   WS_CHECK_LAUNCH("wsovod_f16mx_to_f32");
+  return WSOVOD_OK;
+}
+
+int wsovod_f16mx_range(const void* src, long long ld, int rows, int cols, long long* counters, wsovod_stream_t stream) {
+  WS_CHECK_ARG(rows >= 0 && cols >= 0 && cols % 32 == 0,
+               "wsovod_f16mx_range: rows=%d must not be negative, cols=%d a non-negative multiple of 32", rows, cols);
+  if (rows == 0 || cols == 0) return WSOVOD_OK;
+  WS_CHECK_ARG(src && counters && ld >= cols && ld % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)counters & 7) == 0,
+               "wsovod_f16mx_range: bad pointer / leading dimension");
+  static int slot = wsovod::prof_slot("f16mx_range");
+  hipStream_t s = (hipStream_t)stream;
+  const long long chunks = (long long)rows * (cols / 4);
+  wsovod::ProfScope prof(slot, s, 0.0, (double)rows * cols * 3.0);  // (three of a value's four bytes are read)
+  // a lane takes four chunks per step; at most 2048 workgroups (8 per CU), which also bounds the atomics of a launch
+  const int grid = (int)std::max<long long>(1, std::min<long long>(ceil_div_ll(chunks, 256 * 4), 2048));
+  hipLaunchKernelGGL(mx_range_kernel, dim3(grid), dim3(256), 0, s, (const char*)src, ld * 4, rows, cols,
+                     (unsigned long long*)counters);
+  WS_CHECK_LAUNCH("wsovod_f16mx_range");
   return WSOVOD_OK;
 }
 

@@ -77,4 +77,27 @@ __device__ __forceinline__ void mx_store4_unit(char* row, int k, const f32x4 v) 
   *(int*)(g + 96 + w) = ql;
 }
 
+
+// Range audit (include/wsovod_hip.h: wsovod_f16mx_range).  A 128-byte group is eight 16-byte chunks: 0 - 3 the fp16 hi plane, 4 - 5
+// the q plane, 6 - 7 ql (never loaded).  One instruction stream serves both loaded planes, told apart by three constants:
+//   hi  b = (w & 0x7fff7fff) + 0x04000400: per half |h| + 0x0400, bit 15 set exactly when the exponent field is all ones; as a
+//       signed half every non-finite value is negative, so a signed packed maximum keeps the largest FINITE |h| (+ 0x0400)
+//   q   b = (w & 0x7e7e7e7e) + 0x02020202: per byte bit 7 set exactly when (byte & 0x7f) >= 0x7e, the format's top code 448 or NaN
+// (no sum carries into the neighbouring half / byte; a zero word counts nothing and leaves the maximum alone)
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+struct mx_range_role {
+  unsigned keep, bias, flag;
+};
+__device__ __forceinline__ mx_range_role mx_range_role_of(int chunk) {
+  if (chunk < 4) return {0x7fff7fffu, 0x04000400u, 0x80008000u};
+  if (chunk < 6) return {0x7e7e7e7eu, 0x02020202u, 0x80808080u};
+  return {0u, 0u, 0u};
+}
+constexpr short kMxRangeMaxBias = 0x0400;
+__device__ __forceinline__ void mx_range_word(unsigned w, const mx_range_role r, int& flagged, s16x2& top) {
+  const unsigned b = (w & r.keep) + r.bias;
+  flagged += __builtin_popcount(b & r.flag);
+  top = __builtin_elementwise_max(top, __builtin_bit_cast(s16x2, b));
+}
+
 }  // namespace wsovod_mx

@@ -166,14 +166,24 @@ def wrap_model_with_ddp(model, local_rank, find_unused_parameters=False, bucket_
 
 def run_step(model, optimizer, data, iter_size=1, it=0):
     """One iteration of DefaultTrainer_WSOVOD.run_step.  Returns the loss dict (device tensors)."""
-    loss_dict = model(data)
-    losses = sum(loss_dict.values())
-    if iter_size > 1:
-        losses = losses / iter_size
-    losses.backward()
-    if it % iter_size == 0:
-        optimizer.step()
-        optimizer.zero_grad(set_to_none=True)
+    inner = getattr(model, "module", model)  # (a DistributedDataParallel wrapper)
+    guard = getattr(inner, "mx_guard", None)
+    armed = guard is not None and guard.begin_step()  # MODEL.HIP.MX_RANGE_GUARD: this step's f16mx operands are audited
+    try:
+        loss_dict = model(data)
+        losses = sum(loss_dict.values())
+        if iter_size > 1:
+            losses = losses / iter_size
+        losses.backward()
+        step_now = it % iter_size == 0
+        if step_now:
+            optimizer.step()
+            optimizer.zero_grad(set_to_none=True)
+        if armed:
+            inner.mx_guard_end_step(updated=step_now)  # (one host read; raises MxRangeError by the mode)
+    finally:
+        if armed:
+            guard.arm(False)
     return loss_dict
 
 
@@ -543,6 +553,7 @@ class HotPathTrainer:
         # the WHOLE step as captured HIP graph(s) at small batches (WSOVOD_STEP_GRAPH=0: eager launches + backbone graph)
         self.graph_max_batch = 8 if os.environ.get("WSOVOD_STEP_GRAPH", "1") != "0" else 0
         self._graphs, self._graph_seen = {}, {}
+        self._mx_on_seen = getattr(model, "mx_on", None)  # (the f16mx kernels are selected: what the graphs below captured)
         self._graph_evicted, self._graph_recaptures = set(), 0
         self.iter = int(start_iter)  # the reference's global iteration (engine/trainer.py:72-84): pass it when resuming
         if self.iter_size < 1:
@@ -621,6 +632,12 @@ class HotPathTrainer:
         bb = getattr(self.model, "backbone", None)
         if bb is not None:
             bb.__dict__.pop("_graphs", None)
+
+    def _drop_mx_graphs(self):
+        """The range guard fell back: the captured graphs replay the f16mx kernels.  Every layout starts over -- its bf16x2
+        kernels run eagerly first (their workspaces cannot grow under a capture) and are captured at the usual sighting."""
+        self._drop_graphs()
+        self._graph_seen.clear()
 
     def broadcast_parameters(self, src=0):
         if self.exchange:
@@ -1041,12 +1058,35 @@ class HotPathTrainer:
             operand_cache.replayed(p)
 
     def run_step(self, data):
+        guard = getattr(self.model, "mx_guard", None)
+        mx_on = getattr(self.model, "mx_on", None)
+        if mx_on != self._mx_on_seen:
+            # the range guard fell back to the bf16x2 kernels since the last step -- in this trainer's own armed step or in an
+            # inference() call between steps: every captured graph replays the f16mx kernels and is dropped
+            self._mx_on_seen = mx_on
+            self._drop_mx_graphs()
+        if guard is not None and guard.begin_step():
+            # MODEL.HIP.MX_RANGE_GUARD: an audited step runs on eager launches (no captured graph holds the audit kernels) and
+            # ends with its update applied, the trained weights' operands audited and ONE host read of the guard's table
+            try:
+                step_now = self.iter % self.iter_size == 0  # (else the step only accumulates: no update to apply)
+                out = self._run_step_eager(data)
+                self._finish_pending()
+                if self.model.mx_guard_end_step(updated=step_now) == "fallback":
+                    self._mx_on_seen = self.model.mx_on
+                    self._drop_mx_graphs()
+            finally:
+                guard.arm(False)
+            return out
         g = self._graph_for(data)
         if g is not None:
             out = g.step(data)
             if out is not None:
                 self.iter += 1
                 return out
+        return self._run_step_eager(data)
+
+    def _run_step_eager(self, data):
         done = self._bracket("frozen")
         st = self.model.forward_frozen(data)
         if done is not None:

@@ -450,6 +450,35 @@ def f16mx_to_f32(x):
     return out.view(x.shape)
 
 
+def mx_range(x, counters, operand=False):
+    """Range audit of an f16mx matrix by its bytes (wsovod_f16mx_range): ADDS into the four int64 device counters [values,
+    non-finite hi, q at the format's top code, max finite |hi| as fp16 bits] (layers/mx_guard.py holds a row per site).  x: a
+    tensor RECORDED as a unit-scale f16mx carrier, whole 32-value groups along its rows; operand=True: the carrier of a weight's
+    f16mx operand (mx_encode / mx_cached: scaled, never tagged) is taken as it is."""
+    require_gpu(x, counters)
+    if not operand:
+        carrier.refuse("mx_range", (x,), reads=(MX,))
+        if carrier.fmt_of(x) != MX:
+            raise RuntimeError("wsovod_hip mx_range: got a tensor that is not recorded as an f16mx carrier")
+    if x.dtype != torch.float32:
+        raise RuntimeError("wsovod_hip mx_range: an f16mx carrier is float32-typed")
+    if counters.dtype != torch.int64 or counters.numel() != 4 or not counters.is_contiguous():
+        raise RuntimeError("wsovod_hip mx_range: counters must be 4 contiguous int64 values")
+    if x.dim() == 2 and x.stride(1) == 1:
+        src = x  # (a row block / column block of a wider carrier: ld > cols)
+    elif x.is_contiguous() and x.dim() >= 1:
+        # groups of 32 run along the innermost axis (an NHWC map) or along the flattened row (the pooled tensor)
+        src = x.view(-1, x.shape[-1]) if x.shape[-1] % 32 == 0 else x.view(x.shape[0], -1)
+    else:
+        raise RuntimeError("wsovod_hip mx_range: a contiguous carrier, or a 2-D one with a contiguous last dim, expected")
+    rows, cols = src.shape
+    if cols % 32:
+        raise RuntimeError("wsovod_hip mx_range: rows of whole 32-value groups expected")
+    check(lib().wsovod_f16mx_range(ptr(src), src.stride(0) if rows > 1 else cols, rows, cols, ptr(counters), stream()),
+          "f16mx_range")
+    return counters
+
+
 def mx_from_x2(src):
     """interleaved bf16x2 tensor -> unit-scale f16mx tensor of the same shape (wsovod_f16mx_from_bf16x2)."""
     require_gpu(src)

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import BACKBONE_REGISTRY
-from ..layers import carrier, hip_ops as H
+from ..layers import carrier, hip_ops as H, mx_guard
 from ..structures import ShapeSpec
 
 __all__ = ["BasicStem", "BasicBlock", "BottleneckBlock", "ResNet", "FrozenBatchNorm2d", "Conv2d",
@@ -168,6 +168,8 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
             assert res2d is None or H.mx_of(residual)
             out = H.gemm_mx(x, None, wm, ws, conv=geom, bias=b, relu=relu, residual=res2d,
                             residual_fmt=H.MX if res2d is not None else None, out_dtype=fmt)
+        if fmt == H.MX:
+            mx_guard.audit(conv, out)
         return out.view(N, Ho, Wo, conv.out_channels)  # (a whole view of what gemm_mx tagged)
     if _x2():
         # x (and residual / shortcut input) are bf16x2 maps; three-MFMA products on the bf16x2 weights; the output is
@@ -775,6 +777,7 @@ class ResNet(nn.Module):
                 # the map that crosses from the bf16x2 layers to the f16mx ones (enough 256-row tiles: see _mx_from)
                 with torch.no_grad():
                     x = H.mx_from_x2(x)
+                    mx_guard.audit("backbone.mx_from_x2", x)
             if torch.is_grad_enabled() and any(p.requires_grad for p in params):
                 _warn_trainable_stage_once(name)
                 x = _TrainableStage.apply(stage, H.x3_active(), x, *params)

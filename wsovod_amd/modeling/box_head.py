@@ -13,6 +13,7 @@ from torch import nn
 from ..config import ROI_BOX_HEAD_REGISTRY, configurable
 from ..layers import functions as Fn
 from ..layers import hip_ops as H
+from ..layers import mx_guard
 from ..structures import ShapeSpec
 
 __all__ = ["DiscriminativeAdaptationNeck", "build_box_head"]
@@ -104,6 +105,8 @@ class DiscriminativeAdaptationNeck(nn.Sequential):
                 fmt = H.MX if (H.mx_of(x) and k + 1 < len(self.fcs)) else H.X2
             x = Fn.linear(x, fc.weight, fc.bias, relu=True, dropout_p=p, seed=seed, out_dtype=fmt,
                           seed_add=step_term if p > 0 else None)
+            if fmt == H.MX:
+                mx_guard.audit(fc, x)
         return x
 
     @property

@@ -17,6 +17,7 @@ from torch import nn
 
 from ..config import BACKBONE_REGISTRY, META_ARCH_REGISTRY, configurable
 from ..layers import hip_ops as H
+from ..layers import mx_guard, operand_cache
 from ..structures import Boxes, ImageList, Instances, ShapeSpec
 from .class_heads import DataAwareFeaturesHead
 from .fast_rcnn_open_vocabulary import segment_offsets
@@ -74,6 +75,12 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         # f16mx kernels (layers/hip_ops.py:mx_mode); every module sees "parity", this flag selects the kernels
         # "parity_mx_train": both flags -- the f16mx forward, and input-gradient contractions that keep the hi/lo split
         self.mx = bool(cfg is not None and cfg.MODEL.HIP.PRECISION in ("parity_mx", "parity_mx_train"))
+        # MODEL.HIP.MX_RANGE_GUARD: None = "off" (no audit is ever launched); refused for a precision without f16mx operands
+        self.mx_guard = mx_guard.from_config(cfg) if cfg is not None else None
+        if self.mx_guard is not None:
+            self.mx_guard.names.update({id(m): n for n, m in self.named_modules() if n})
+            guard = self.mx_guard
+            self.register_load_state_dict_post_hook(lambda *_a, **_k: guard.rearm())  # (holds the guard, not the model)
 
     @classmethod
     def from_config(cls, cfg):
@@ -190,9 +197,33 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         themselves -- no stand-alone split passes, no fp32 activation traffic -- and a plain bf16 backward."""
         return {"bf16x3": "full", "bf16x3f": "fwd", "parity": "x2"}.get(getattr(self.backbone, "precision", "bf16"), False)
 
+    @property
+    def mx_on(self):
+        """The f16mx kernels are selected: the precision asks for them and the range guard has not fallen back to bf16x2."""
+        g = getattr(self, "mx_guard", None)
+        return bool(getattr(self, "mx", False)) and not (g is not None and g.fallen_back)
+
+    def _guarded(self):
+        """Context of every model entry point: this model's range guard is the calling thread's active one."""
+        return mx_guard.active(getattr(self, "mx_guard", None))
+
+    def mx_guard_end_step(self, updated=True):
+        """End of an ARMED training step: audit the f16mx operands of the trained weights (after the step's update, the bytes
+        the optimizer kernels refreshed), poll, and act by the mode -> "ok" / "warn" / "fallback" (the caller drops what it
+        captured of the f16mx kernels).  updated: the step applied an optimizer update (False: it only accumulated gradients;
+        a non-finite hi then follows the mode like a saturated one)."""
+        g = self.mx_guard
+        if g is None or not g.armed():
+            return "ok"
+        for name, p in self.named_parameters():
+            op = operand_cache.one_scale_mx(p) if p.requires_grad else None
+            if op is not None:
+                g.audit("weight:" + name, op[0], operand=True)
+        return g.settle(g.poll(), updated=updated, training=True)
+
     @torch.no_grad()
     def forward_frozen(self, batched_inputs):
-        with H.x3_mode(self.x3), H.mx_mode(getattr(self, "mx", False)):
+        with H.x3_mode(self.x3), H.mx_mode(self.mx_on), self._guarded():
             return self._forward_frozen(batched_inputs)
 
     def forward_trainable(self, st):
@@ -203,7 +234,7 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
                 'MODEL.HIP.PRECISION "parity_mx_train" needs a frozen backbone (MODEL.BACKBONE.FREEZE_AT = 5, as in every '
                 "shipped WSR config): its split input gradients stop at the pooled tensor, and a trainable stage would "
                 'continue them through convolution backwards that keep no hi/lo split -- use "parity_train" or "parity_mx"')
-        with H.x3_mode(self.x3), backward_split(self.backward_split), H.mx_mode(getattr(self, "mx", False)):
+        with H.x3_mode(self.x3), backward_split(self.backward_split), H.mx_mode(self.mx_on), self._guarded():
             return self._forward_trainable(st)
 
     @torch.no_grad()
@@ -211,7 +242,26 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         pre = getattr(self, "_pre_inference", None)  # an overlapped trainer applies its pending update first (eval / TTA
         if pre is not None:                          # hooks between steps must see the weights after optimizer.step())
             pre()
-        with H.x3_mode(self.x3), H.mx_mode(getattr(self, "mx", False)):
+        g = getattr(self, "mx_guard", None)
+        if g is None or not self.mx_on:
+            with H.x3_mode(self.x3), H.mx_mode(self.mx_on):
+                return self._inference(batched_inputs, detected_instances, do_postprocess, classifier)
+        # MODEL.HIP.MX_RANGE_GUARD: every inference call is audited; the table is read after the eval tail's own host read
+        # (the detections' counts), so the poll waits for nothing
+        g.arm()
+        g.reset()
+        counter = self.roi_heads.iter_test
+        try:
+            with H.x3_mode(self.x3), H.mx_mode(True), self._guarded():
+                out = self._inference(batched_inputs, detected_instances, do_postprocess, classifier)
+            verdict = g.settle(g.poll())
+        finally:
+            g.arm(False)
+        if verdict != "fallback":
+            return out
+        # THIS batch again on the bf16x2 kernels ("parity": bf16 has fp32's exponent range); sticky -- mx_on is False from now on
+        self.roi_heads.iter_test = counter
+        with H.x3_mode(self.x3), H.mx_mode(False):
             return self._inference(batched_inputs, detected_instances, do_postprocess, classifier)
 
     def _forward_frozen(self, batched_inputs):
@@ -236,7 +286,8 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
             st["sizes_t"] = sizes_t
             st["features"] = st["gaps"] = st["pooled"] = None
             return st
-        features = self.backbone.forward_uint8(canvas, sizes_t, self._mean, self._std, allow_graph=True)
+        # (a step the range guard audits keeps the eager launches: a replayed backbone graph holds no audit)
+        features = self.backbone.forward_uint8(canvas, sizes_t, self._mean, self._std, allow_graph=not mx_guard.launching())
         st["features"] = features
         pool_here = self.proposal_generator is None  # with an RPN the box set depends on trainable weights: pooling moves
         fuse = contextlib.nullcontext()               # to the trainable part

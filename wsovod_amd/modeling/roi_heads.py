@@ -23,6 +23,7 @@ from torch import nn
 from ..config import ROI_HEADS_REGISTRY, configurable
 from ..layers import functions as Fn
 from ..layers import hip_ops as H
+from ..layers import mx_guard
 from ..structures import Boxes, ImageList, Instances, ShapeSpec
 from .backbone import forward_precision
 from .box_head import build_box_head
@@ -279,8 +280,11 @@ class WSOVODROIHeads(ROIHeads):
             return (out * roi_scale.repeat(3).view(-1, 1, 1, 1)).to(self.compute_dtype)
         Fn._WANT_HI.on = self.training and os.environ.get("WSOVOD_X2_HI", "1") != "0"  # (bf16x2 pooling only) a plain bf16 copy for fc1's dW
         try:
-            return self.box_pooler(feats, [x.proposal_boxes for x in proposals], roi_scale=roi_scale,
-                                   out_dtype=self._pool_dtype_for(int(rois.shape[0])), rois=rois)
+            pooled = self.box_pooler(feats, [x.proposal_boxes for x in proposals], roi_scale=roi_scale,
+                                     out_dtype=self._pool_dtype_for(int(rois.shape[0])), rois=rois)
+            if H.mx_of(pooled):
+                mx_guard.audit("roi_heads.pooled", pooled)
+            return pooled
         finally:
             Fn._WANT_HI.on = False
 

@@ -263,9 +263,30 @@ int wsovod_stem_im2col(const unsigned char* img, const int* sizes, const float* 
 int wsovod_stem_conv1(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host, int N,
                       int Hp, int Wp, const void* w32, const float* bias, void* out, wsovod_stream_t stream);
 
+/* The STRIDE-1 first conv of the VGG16 backbone (conv1_1: Conv2d(3, 64, 3, stride 1, padding 1, bias) + relu_,
+ * wsovod/modeling/backbone/vgg.py:44-55,103-105, on the image of rcnn_wsovod.py:321-328) with the contract of the stride-2
+ * entry points: the same normalisation table, zero outside image n's own (h, w) AFTER normalisation, k = (r*3+q)*3+c with 27
+ * taps + 5 zero columns, bias + ReLU in the epilogue; Ho = Hp, Wo = Wp.
+ *   wsovod_stem_im2col_ex   wsovod_stem_im2col with `stride` = 1 or 2 (stride 2: the same bytes): the (N*Ho*Wo, 32) operand of
+ *                           the fp32 / bf16x3 precisions, and what the fused bf16 kernel matches bit for bit
+ *   wsovod_stem_conv1_s1    w32 = the [64][32] bf16 weight -> (N, Hp, Wp, 64) bf16 NHWC
+ *   wsovod_stem_conv1_s1_x2 w32x2 = the bf16x2 encoding of the (64, 32) fp32 weight -> (N, Hp, Wp, 64) bf16x2 NHWC,
+ *                           [hi 0-31 | lo 0-31 | hi 32-63 | lo 32-63] per pixel, three-MFMA products
+ * The output (123 MB per 800 x 600 image in bf16x2) is addressed with 64-bit offsets: no 2 GiB limit of its own. */
+int wsovod_stem_im2col_ex(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host, int N,
+                          int Hp, int Wp, int stride, void* out, int out_dtype, wsovod_stream_t stream);
+int wsovod_stem_conv1_s1(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host, int N,
+                         int Hp, int Wp, const void* w32, const float* bias, void* out, wsovod_stream_t stream);
+int wsovod_stem_conv1_s1_x2(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host, int N,
+                            int Hp, int Wp, const void* w32x2, const float* bias, void* out, wsovod_stream_t stream);
+
 /* 2x2 max pool over NHWC, stride 1 or 2; zero_pad_br=1 first pads one zero row/column at the
  * bottom/right (nn.ZeroPad2d((0,1,0,1)) + MaxPool2d(2, 1)).  Replaces the pools of
- * resnet_wsl.py:85-92,408. */
+ * resnet_wsl.py:85-92,408, and nn.MaxPool2d(2, stride, padding=0) of vgg.py:98-99,118-119 (zero_pad_br=0, stride 1: the map
+ * shrinks by one row and one column; odd sizes floor).
+ * dtype = WSOVOD_BF16X2 / WSOVOD_F16MX (unit scale): C a multiple of 32; elements are compared by the value they stand for
+ * (hi + lo / hi + ql 2^-11), the FIRST maximum in scan order (0,0), (0,1), (1,0), (1,1) wins (strict '>'), and the winner's
+ * fields (f16mx: fp16 hi, e4m3 q, e4m3 ql) are copied verbatim -- no re-encode; a padded zero cell is the all-zero element. */
 int wsovod_maxpool2x2_nhwc(const void* in, int dtype, int N, int H, int W, int C, int stride,
                            int zero_pad_br, void* out, wsovod_stream_t stream);
 /* Its backward (round 6; a trainable res2 / res3 stage, resnet_wsl.py:85-92,530-552 under autograd): din (N,H,W,C) fp32 =

@@ -72,6 +72,9 @@ SIGNATURES = {
     "wsovod_preprocess_image": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
     "wsovod_stem_im2col": [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P],
     "wsovod_stem_conv1": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "wsovod_stem_im2col_ex": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P],
+    "wsovod_stem_conv1_s1": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "wsovod_stem_conv1_s1_x2": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "wsovod_maxpool2x2_nhwc": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "wsovod_maxpool2x2_nhwc_backward": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "wsovod_global_avgpool_nhwc": [_P, _I, _I, _I, _I, _P, _P, _P],

@@ -4,7 +4,7 @@ Provides `CfgNode` (attribute dict with `merge_from_file` honouring `_BASE_`, an
 `merge_from_list`), `get_cfg()` = the subset of detectron2's defaults the hot path reads
 (last row) + the reference's `add_wsovod_config`
 (/root/reference/wsovod/config/defaults.py:7-96) so that the reference's own YAML files
-(configs/*/WSOVOD_WSR_{18,50}_DC5_1x.yaml) load unchanged, plus `configurable` and `Registry`.
+(configs/*/WSOVOD_WSR_{18,50}_DC5_1x.yaml, configs/*/WSOVOD_V_16_DC5*_1x.yaml) load unchanged, plus `configurable` and `Registry`.
 """
 import copy
 import functools
@@ -222,6 +222,8 @@ def add_wsovod_config(cfg):
     _C.MODEL.ROI_BOX_HEAD.OPEN_VOCABULARY.NORM_TEMP = 100.0
     _C.MODEL.ROI_BOX_HEAD.OPEN_VOCABULARY.DATA_AWARE = False
     _C.MODEL.ROI_BOX_HEAD.OPEN_VOCABULARY.PROTOTYPE_NUM = 5
+    # the VGG16 backbone of the V_16 configs (defaults.py:35-39; modeling/backbone_vgg.py)
+    _C.MODEL.VGG = C({"DEPTH": 16, "OUT_FEATURES": ["plain5"], "CONV5_DILATION": 1})
     _C.MODEL.MRRP = C({"MRRP_ON": False, "NUM_BRANCH": 3, "BRANCH_DILATIONS": [1, 2, 3],
                        "MRRP_STAGE": "res4", "TEST_BRANCH_IDX": 1})
     _C.DATASETS.MIXED_DATASETS = C()

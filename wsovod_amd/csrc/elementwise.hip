@@ -43,7 +43,7 @@ __global__ void preprocess_nchw_kernel(const uint8_t* __restrict__ img, const in
 template <typename T>
 __global__ void stem_im2col_kernel(const uint8_t* __restrict__ img, const int* __restrict__ sizes, float m0,
                                    float m1, float m2, float s0, float s1, float s2, int N, int Hp, int Wp, int Ho,
-                                   int Wo, T* __restrict__ out) {
+                                   int Wo, int stride, T* __restrict__ out) {
   const long long total = (long long)N * Ho * Wo * 32;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
@@ -55,7 +55,7 @@ __global__ void stem_im2col_kernel(const uint8_t* __restrict__ img, const int* _
     float v = 0.f;
     if (k < 27) {
       const int c = k % 3, tap = k / 3, r = tap / 3, q = tap % 3;
-      const int h = ho * 2 - 1 + r, w = wo * 2 - 1 + q;
+      const int h = ho * stride - 1 + r, w = wo * stride - 1 + q;
       if (h >= 0 && w >= 0 && h < sizes[2 * n] && w < sizes[2 * n + 1]) {
         const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2);
         const float sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
@@ -110,6 +110,71 @@ __global__ void maxpool2x2_nhwc_kernel(const T* __restrict__ in, int N, int H, i
 #pragma unroll
     for (int j = 0; j < V; ++j) oe[j] = from_f32<T>(best[j]);
     *(uint4*)(out + (((long long)n * Ho + ho) * Wo + wo) * C + c) = o;
+  }
+}
+
+// The same pool on a unit-scale f16mx map (csrc/f16mx.h; the pools between the f16mx layers of the VGG16 backbone,
+// vgg.py:98-99,118-119).  Elements are compared by the value they stand for, hi + ql 2^-11 (exact in fp32: 11 + 4 bits), the
+// FIRST maximum in scan order (0,0), (0,1), (1,0), (1,1) with strict '>' wins (the backward's rule above), and the winner's
+// three fields -- fp16 hi, e4m3 q, e4m3 ql -- are COPIED, never re-encoded: the output is a valid carrier whose cross-term
+// planes are exactly the producer's.  A padded zero cell is the all-zero triple.  8 values per lane: 16 B of hi, 8 B of q, 8 B
+// of ql of one 128-byte group.
+__global__ void mx_maxpool2x2_kernel(const char* __restrict__ in, int N, int H, int W, int C, int Ho, int Wo, int stride,
+                                     int zero_pad, char* __restrict__ out) {
+  typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+  const int cv = C >> 3;
+  const long long total = (long long)N * Ho * Wo * cv;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % cv) * 8;
+    const int wo = (int)((i / cv) % Wo);
+    const int ho = (int)((i / ((long long)cv * Wo)) % Ho);
+    const int n = (int)(i / ((long long)cv * Wo * Ho));
+    const long long goff = wsovod_mx::mx_group(c);
+    const int w32 = c & 31;
+    u16x8 bh;
+    unsigned char bq[8], bl[8];
+    float best[8];
+    bool any = false;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const int h = ho * stride + dy, w = wo * stride + dx;
+        u16x8 vh = {0, 0, 0, 0, 0, 0, 0, 0};
+        wsovod_mx::i32x2 vq = {0, 0}, vl = {0, 0};
+        if (h < H && w < W) {
+          const char* g = in + (((long long)n * H + h) * W + w) * 4 * C + goff;
+          vh = *(const u16x8*)(g + 2 * w32);
+          vq = *(const wsovod_mx::i32x2*)(g + 64 + w32);
+          vl = *(const wsovod_mx::i32x2*)(g + 96 + w32);
+        } else if (!zero_pad) {
+          continue;
+        }
+        const wsovod_mx::f16x8 fh = __builtin_bit_cast(wsovod_mx::f16x8, vh);
+        const f32x4 a = wsovod_mx::mx_dec4_unit(wsovod_mx::f16x4{fh[0], fh[1], fh[2], fh[3]}, vl[0]);
+        const f32x4 b = wsovod_mx::mx_dec4_unit(wsovod_mx::f16x4{fh[4], fh[5], fh[6], fh[7]}, vl[1]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float v = j < 4 ? a[j & 3] : b[j & 3];
+          if (!any || v > best[j]) {
+            best[j] = v;
+            bh[j] = vh[j];
+            bq[j] = (unsigned char)((unsigned)vq[j >> 2] >> (8 * (j & 3)));
+            bl[j] = (unsigned char)((unsigned)vl[j >> 2] >> (8 * (j & 3)));
+          }
+        }
+        any = true;
+      }
+    wsovod_mx::i32x2 oq, ol;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      oq[k] = (int)((unsigned)bq[4 * k] | (unsigned)bq[4 * k + 1] << 8 | (unsigned)bq[4 * k + 2] << 16 | (unsigned)bq[4 * k + 3] << 24);
+      ol[k] = (int)((unsigned)bl[4 * k] | (unsigned)bl[4 * k + 1] << 8 | (unsigned)bl[4 * k + 2] << 16 | (unsigned)bl[4 * k + 3] << 24);
+    }
+    char* o = out + (((long long)n * Ho + ho) * Wo + wo) * 4 * C + goff;
+    *(u16x8*)(o + 2 * w32) = bh;
+    *(wsovod_mx::i32x2*)(o + 64 + w32) = oq;
+    *(wsovod_mx::i32x2*)(o + 96 + w32) = ol;
   }
 }
 
@@ -1239,41 +1304,56 @@ int wsovod_preprocess_image(const unsigned char* img, const int* sizes, const fl
   return WSOVOD_OK;
 }
 
-int wsovod_stem_im2col(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host,
-                       int N, int Hp, int Wp, void* out, int out_dtype, wsovod_stream_t stream) {
+int wsovod_stem_im2col_ex(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host,
+                          int N, int Hp, int Wp, int stride, void* out, int out_dtype, wsovod_stream_t stream) {
   WS_CHECK_ARG(N >= 0 && Hp > 0 && Wp > 0, "wsovod_stem_im2col: bad shape");
+  WS_CHECK_ARG(stride == 1 || stride == 2, "wsovod_stem_im2col: stride must be 1 or 2");
   if (N == 0) return WSOVOD_OK;
   WS_CHECK_ARG(img && sizes && mean_host && std_host && out, "wsovod_stem_im2col: null pointer");
   WS_CHECK_ARG(out_dtype == WSOVOD_F32 || out_dtype == WSOVOD_BF16, "wsovod_stem_im2col: bad dtype");
   static int slot = wsovod::prof_slot("stem_im2col");
   hipStream_t s = (hipStream_t)stream;
-  const int Ho = (Hp - 1) / 2 + 1, Wo = (Wp - 1) / 2 + 1;
+  const int Ho = (Hp - 1) / stride + 1, Wo = (Wp - 1) / stride + 1;
   const long long total = (long long)N * Ho * Wo * 32;
   wsovod::ProfScope prof(slot, s, 0.0, (double)N * 3 * Hp * Wp + total * (out_dtype == WSOVOD_BF16 ? 2.0 : 4.0));
   if (out_dtype == WSOVOD_BF16)
     hipLaunchKernelGGL(stem_im2col_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, s, img, sizes,
                        mean_host[0], mean_host[1], mean_host[2], std_host[0], std_host[1], std_host[2], N, Hp, Wp, Ho,
-                       Wo, (bf16_t*)out);
+                       Wo, stride, (bf16_t*)out);
   else
     hipLaunchKernelGGL(stem_im2col_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, s, img, sizes,
                        mean_host[0], mean_host[1], mean_host[2], std_host[0], std_host[1], std_host[2], N, Hp, Wp, Ho,
-                       Wo, (float*)out);
+                       Wo, stride, (float*)out);
   WS_CHECK_LAUNCH("wsovod_stem_im2col");
   return WSOVOD_OK;
 }
 
+int wsovod_stem_im2col(const unsigned char* img, const int* sizes, const float* mean_host, const float* std_host,
+                       int N, int Hp, int Wp, void* out, int out_dtype, wsovod_stream_t stream) {
+  return wsovod_stem_im2col_ex(img, sizes, mean_host, std_host, N, Hp, Wp, 2, out, out_dtype, stream);
+}
+
 int wsovod_maxpool2x2_nhwc(const void* in, int dtype, int N, int H, int W, int C, int stride, int zero_pad_br,
                            void* out, wsovod_stream_t stream) {
-  WS_CHECK_ARG(dtype == WSOVOD_F32 || dtype == WSOVOD_BF16 || dtype == WSOVOD_BF16X2, "wsovod_maxpool2x2_nhwc: bad dtype");
+  WS_CHECK_ARG(dtype == WSOVOD_F32 || dtype == WSOVOD_BF16 || dtype == WSOVOD_BF16X2 || dtype == WSOVOD_F16MX,
+               "wsovod_maxpool2x2_nhwc: bad dtype");
   WS_CHECK_ARG(stride == 1 || stride == 2, "wsovod_maxpool2x2_nhwc: stride must be 1 or 2");
-  const int V = dtype == WSOVOD_BF16 ? 8 : dtype == WSOVOD_BF16X2 ? 32 : 4;
+  const int V = dtype == WSOVOD_BF16 ? 8 : (dtype == WSOVOD_BF16X2 || dtype == WSOVOD_F16MX) ? 32 : 4;
   WS_CHECK_ARG(C % V == 0, "wsovod_maxpool2x2_nhwc: C=%d must be a multiple of %d", C, V);
   const int Hin = H + (zero_pad_br ? 1 : 0), Win = W + (zero_pad_br ? 1 : 0);
   const int Ho = (Hin - 2) / stride + 1, Wo = (Win - 2) / stride + 1;
   if (N == 0 || Ho <= 0 || Wo <= 0) return WSOVOD_OK;
   WS_CHECK_ARG(in && out, "wsovod_maxpool2x2_nhwc: null pointer");
-  static int slot = wsovod::prof_slot("maxpool2x2_nhwc");
   hipStream_t s = (hipStream_t)stream;
+  if (dtype == WSOVOD_F16MX) {  // (a profile row of its own: the f16mx layers' pools are told apart from the bf16x2 ones)
+    static int slot_mx = wsovod::prof_slot("maxpool2x2_nhwc_f16mx");
+    wsovod::ProfScope prof(slot_mx, s, 0.0, ((double)N * H * W * C + (double)N * Ho * Wo * C) * 4.0);
+    hipLaunchKernelGGL(mx_maxpool2x2_kernel, dim3(grid_for((long long)N * Ho * Wo * (C / 8), 256)), dim3(256), 0, s,
+                       (const char*)in, N, H, W, C, Ho, Wo, stride, zero_pad_br, (char*)out);
+    WS_CHECK_LAUNCH("wsovod_maxpool2x2_nhwc");
+    return WSOVOD_OK;
+  }
+  static int slot = wsovod::prof_slot("maxpool2x2_nhwc");
   const long long total = (long long)N * Ho * Wo * (C / V);
   const double esz = dtype == WSOVOD_BF16 ? 2.0 : 4.0;
   wsovod::ProfScope prof(slot, s, 0.0, ((double)N * H * W * C + (double)N * Ho * Wo * C) * esz);

@@ -13,6 +13,11 @@ no copy).  The kernel fronts that WRITE a carrier tag it (`tag`, the only place 
 `fmt_of` / `hi_of`; a consumer that reads another format refuses (`refuse`).  A tensor that is not float32-typed is never a
 carrier -- the bfloat16 view of a planar carrier's hi plane is a plain bf16 matrix.
 
+Writers (kernel fronts in layers/hip_ops.py that tag their output): x2_encode / x2_encode_t, mx_encode(unit=True), mx_from_x2,
+gemm_nt / gemm_mx with a carrier `out_dtype`, the RoI poolers, stem_conv1_x2 / stem_conv1_s1_x2 (X2), add_group_rows, and
+maxpool2x2_nhwc (x2= -> X2; mx= -> MX: the f16mx pool copies the winner's fields, its output is a carrier of the same format).
+Readers that take MX: gemm_mx, maxpool2x2_nhwc(mx=True), f16mx_to_f32, mx_range; everything else reads X2 / fp32 and refuses.
+
 Which torch operations keep the tag (tests/test_carrier.py pins each):
 
     kept     whole views -- `view`, `flatten`, `reshape` of a contiguous tensor: `_base` is the tagged tensor, with the same

@@ -853,6 +853,39 @@ def stem_im2col(images_u8, sizes, mean, std, dtype):
     return out, Ho, Wo
 
 
+def stem_im2col_ex(images_u8, sizes, mean, std, dtype, stride):
+    """stem_im2col at `stride` 1 (VGG16's conv1_1: Ho = Hp, Wo = Wp) or 2 (stem_im2col's bytes): wsovod_stem_im2col_ex."""
+    require_gpu(images_u8, sizes)
+    N, _, Hp, Wp = images_u8.shape
+    Ho, Wo = (Hp - 1) // stride + 1, (Wp - 1) // stride + 1
+    out = torch.empty((N * Ho * Wo, 32), dtype=dtype, device=images_u8.device)
+    check(lib().wsovod_stem_im2col_ex(ptr(images_u8), ptr(sizes), _f3(mean), _f3(std), N, Hp, Wp, int(stride), ptr(out),
+                                      dtype_code(dtype), stream()), "stem_im2col_ex")
+    return out, Ho, Wo
+
+
+def stem_conv1_s1(images_u8, sizes, mean, std, w32, bias):
+    """uint8 (N,3,Hp,Wp) images -> relu(conv 3x3/s1 + bias) as (N,Hp,Wp,64) bf16 NHWC (VGG16 conv1_1), no im2col operand."""
+    require_gpu(images_u8, sizes, w32, bias)
+    assert w32.dtype == torch.bfloat16 and tuple(w32.shape) == (64, 32) and w32.is_contiguous()
+    N, _, Hp, Wp = images_u8.shape
+    out = torch.empty((N, Hp, Wp, 64), dtype=torch.bfloat16, device=images_u8.device)
+    check(lib().wsovod_stem_conv1_s1(ptr(images_u8), ptr(sizes), _f3(mean), _f3(std), N, Hp, Wp, ptr(w32), ptr(bias),
+                                     ptr(out), stream()), "stem_conv1_s1")
+    return out
+
+
+def stem_conv1_s1_x2(images_u8, sizes, mean, std, w32_x2, bias):
+    """uint8 (N,3,Hp,Wp) images -> relu(conv 3x3/s1 + bias) as (N,Hp,Wp,64) bf16x2 NHWC (three-MFMA products)."""
+    require_gpu(images_u8, sizes, w32_x2, bias)
+    assert w32_x2.dtype == torch.float32 and tuple(w32_x2.shape) == (64, 32) and w32_x2.is_contiguous()
+    N, _, Hp, Wp = images_u8.shape
+    out = torch.empty((N, Hp, Wp, 64), dtype=torch.float32, device=images_u8.device)
+    check(lib().wsovod_stem_conv1_s1_x2(ptr(images_u8), ptr(sizes), _f3(mean), _f3(std), N, Hp, Wp, ptr(w32_x2), ptr(bias),
+                                        ptr(out), stream()), "stem_conv1_s1_x2")
+    return carrier.tag(out, X2)
+
+
 def stem_conv1(images_u8, sizes, mean, std, w32, bias):
     """uint8 (N,3,Hp,Wp) images -> relu(conv1 3x3/s2 (folded BN)) as (N,Ho,Wo,64) bf16 NHWC, no im2col operand."""
     require_gpu(images_u8, sizes, w32, bias)
@@ -865,16 +898,20 @@ def stem_conv1(images_u8, sizes, mean, std, w32, bias):
     return out
 
 
-def maxpool2x2_nhwc(x, stride, zero_pad_br=False, x2=False):
-    """x: (N,H,W,C) contiguous -> (N,Ho,Wo,C).  x2: x is a bf16x2 map (C a multiple of 32)."""
+def maxpool2x2_nhwc(x, stride, zero_pad_br=False, x2=False, mx=False):
+    """x: (N,H,W,C) contiguous -> (N,Ho,Wo,C).  x2: x is a bf16x2 map; mx: a unit-scale f16mx map (C a multiple of 32): the
+    winner's fields are copied, the output is a carrier of the same format."""
     require_gpu(x)
+    if mx and (x2 or not mx_of(x)):
+        raise RuntimeError("wsovod_hip maxpool2x2_nhwc: mx=True takes a tensor recorded as an f16mx carrier (and no x2=)")
     N, H, W, Cc = x.shape
     Hin, Win = H + int(zero_pad_br), W + int(zero_pad_br)
     Ho, Wo = (Hin - 2) // stride + 1, (Win - 2) // stride + 1
     out = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    check(lib().wsovod_maxpool2x2_nhwc(ptr(x), BF16X2 if x2 else dtype_code(x.dtype), N, H, W, Cc, stride, int(zero_pad_br),
-                                       ptr(out), stream()), "maxpool2x2_nhwc")
-    return carrier.tag(out, X2) if x2 else out
+    code = F16MX if mx else BF16X2 if x2 else dtype_code(x.dtype)
+    check(lib().wsovod_maxpool2x2_nhwc(ptr(x), code, N, H, W, Cc, stride, int(zero_pad_br), ptr(out), stream()),
+          "maxpool2x2_nhwc")
+    return carrier.tag(out, MX) if mx else carrier.tag(out, X2) if x2 else out
 
 
 def maxpool2x2_nhwc_backward(x, dout, stride, zero_pad_br=False, x2=False):

@@ -30,7 +30,7 @@ from ..config import BACKBONE_REGISTRY
 from ..layers import carrier, hip_ops as H, mx_guard
 from ..structures import ShapeSpec
 
-__all__ = ["BasicStem", "BasicBlock", "BottleneckBlock", "ResNet", "FrozenBatchNorm2d", "Conv2d",
+__all__ = ["BasicStem", "BasicBlock", "BottleneckBlock", "ResNet", "FrozenForwardMixin", "FrozenBatchNorm2d", "Conv2d",
            "build_wsl_resnet_backbone", "make_stage"]
 
 
@@ -664,7 +664,94 @@ def _stage_backward_hip(ctx, dy, x, params):
 _TrainableStage._backward_hip = staticmethod(_stage_backward_hip)
 
 
-class ResNet(nn.Module):
+class FrozenForwardMixin:
+    """What the meta-arch and the trainers call on a backbone, shared by `ResNet` and `VGG16` (backbone_vgg.py): the fused
+    uint8 entry with its precision mode, the frozen forward as a HIP graph, the parameter walks cached per module tree.  The
+    class provides `precision`, `_forward_uint8(images_u8, sizes, mean, std)`, `has_trainable_stage` and the
+    `_out_feature_{channels,strides}` / `_out_features` tables."""
+
+    @property
+    def compute_dtype(self):
+        return torch.bfloat16 if self.precision == "bf16" else torch.float32  # "fp32" and "bf16x3" carry fp32 tensors
+
+    def _param_list(self):
+        cached = getattr(self, "_params_cache", None)
+        if cached is None:  # the module tree is fixed after construction: walk it once, not every step
+            cached = self._params_cache = list(self.parameters())
+        return cached
+
+    def _stage_params(self, stage):
+        cache = self.__dict__.setdefault("_stage_params_cache", {})
+        got = cache.get(id(stage))
+        if got is None:  # (fixed after construction, as _param_list)
+            got = cache[id(stage)] = list(stage.parameters())
+        return got
+
+    def forward_uint8(self, images_u8, sizes, pixel_mean, pixel_std, allow_graph=False):
+        """Fused entry used by the meta-arch: uint8 canvas -> normalise + im2col -> stem conv1 GEMM.
+        allow_graph: the caller consumes the maps before its next call with this shape (the training step's frozen
+        forward): small batches may then come from a captured HIP graph, whose outputs are that graph's STATIC buffers
+        -- overwritten by the next replay.  inference() / TTA keep the eager launches (fresh tensors)."""
+        with H.x3_mode({"bf16x3": "full", "bf16x3f": "fwd", "parity": "x2"}.get(self.precision, False)):
+            if allow_graph and self.graph_max_batch and images_u8.is_cuda and images_u8.size(0) <= self.graph_max_batch \
+                    and not self.has_trainable_stage:
+                g = self._graph_for(images_u8, sizes, pixel_mean, pixel_std)
+                if g is not None:
+                    return g(images_u8)
+            return self._forward_uint8(images_u8, sizes, pixel_mean, pixel_std)
+
+    # ---- the frozen forward as a HIP graph (small batches: the ~25 launches of the backbone cost more host time than
+    # device time; one replay instead).  Opt-in (`graph_max_batch`, set by the overlapped trainer): the returned maps
+    # are the graph's static buffers, valid until the next call with the same input shape ----
+    graph_max_batch = 0
+    GRAPH_CACHE = 4  # graphs kept (each holds the backbone's activations of its shape)
+    GRAPH_AFTER = 3  # calls with a shape before it is captured
+
+    def _graph_fingerprint(self):
+        ps = getattr(self, "_graph_tensors", None)
+        if ps is None:
+            ps = self._graph_tensors = list(self.parameters()) + list(self.buffers())
+        return sum(t._version for t in ps), ps[0].data_ptr() if ps else 0
+
+    def _graph_for(self, images_u8, sizes, pixel_mean, pixel_std):
+        from .._lib import PROFILING
+
+        if PROFILING[0] or torch.cuda.is_current_stream_capturing():
+            return None
+        fp = self._graph_fingerprint()
+        cache = self.__dict__.setdefault("_graphs", {})
+        if any(v and v.fingerprint != fp for v in cache.values()):
+            cache.clear()  # a weight changed (load_state_dict, broadcast): the folded copies the graphs point at are stale
+        key = (tuple(images_u8.shape), sizes.data_ptr(), tuple(pixel_mean), tuple(pixel_std), H.x3_active(), H.mx_active())
+        g = cache.get(key)
+        if g is None:
+            # capture on the third call with a shape: with multi-scale inputs most shapes never repeat, and a capture
+            # costs three forwards
+            seen = self.__dict__.setdefault("_graph_seen", {})
+            if len(seen) > 64:
+                seen.clear()
+            seen[key] = seen.get(key, 0) + 1
+            if seen[key] < self.GRAPH_AFTER:
+                return None
+            if len(cache) >= self.GRAPH_CACHE:
+                cache.pop(next(iter(cache)))
+            try:
+                g = _BackboneGraph(self, images_u8, sizes, pixel_mean, pixel_std, fp)
+            except Exception as e:  # noqa: BLE001 -- out of memory in the graph's pool, an API call refused under capture
+                import warnings
+
+                warnings.warn(f"wsovod_amd: HIP graph capture of the frozen backbone failed for input shape "
+                              f"{tuple(images_u8.shape)} ({type(e).__name__}: {e}); this shape keeps the eager launches")
+                g = False  # remembered: never retried for this key
+            cache[key] = g
+        return g or None
+
+    def output_shape(self):
+        return {name: ShapeSpec(channels=self._out_feature_channels[name], stride=self._out_feature_strides[name])
+                for name in self._out_features}
+
+
+class ResNet(FrozenForwardMixin, nn.Module):
     """resnet_wsl.py:424-607."""
 
     def __init__(self, stem, stages, num_classes=None, out_features=None, freeze_at=0, precision="bf16"):
@@ -709,10 +796,6 @@ class ResNet(nn.Module):
     def size_divisibility(self):
         return 0
 
-    @property
-    def compute_dtype(self):
-        return torch.bfloat16 if self.precision == "bf16" else torch.float32  # "fp32" and "bf16x3" carry fp32 tensors
-
     def _check_frozen(self):
         """The generic float entry (`forward(x)`, a normalised float image) has no trainable-stem path: the stem's first conv
         trains through the fused uint8 entry (`forward_uint8`, what the meta-arch calls; _TrainableStem)."""
@@ -726,19 +809,6 @@ class ResNet(nn.Module):
         """True when a residual stage is trainable (FREEZE_AT < 5): the backbone forward then reads weights the optimizer
         updates, and the trainers may no longer run it ahead of the previous step's update."""
         return any(p.requires_grad for p in self._param_list())
-
-    def _param_list(self):
-        cached = getattr(self, "_params_cache", None)
-        if cached is None:  # the module tree is fixed after construction: walk it once, not every step
-            cached = self._params_cache = list(self.parameters())
-        return cached
-
-    def _stage_params(self, stage):
-        cache = self.__dict__.setdefault("_stage_params_cache", {})
-        got = cache.get(id(stage))
-        if got is None:  # (fixed after construction, as _param_list)
-            got = cache[id(stage)] = list(stage.parameters())
-        return got
 
     MX_MIN_TILES = int(os.environ.get("WSOVOD_MX_MIN_TILES", "200"))
 
@@ -803,65 +873,6 @@ class ResNet(nn.Module):
                 xs = self.stem(xn)
             return self._run(xs)
 
-    def forward_uint8(self, images_u8, sizes, pixel_mean, pixel_std, allow_graph=False):
-        """Fused entry used by the meta-arch: uint8 canvas -> normalise + im2col -> stem conv1 GEMM.
-        allow_graph: the caller consumes the maps before its next call with this shape (the training step's frozen
-        forward): small batches may then come from a captured HIP graph, whose outputs are that graph's STATIC buffers
-        -- overwritten by the next replay.  inference() / TTA keep the eager launches (fresh tensors)."""
-        with H.x3_mode({"bf16x3": "full", "bf16x3f": "fwd", "parity": "x2"}.get(self.precision, False)):
-            if allow_graph and self.graph_max_batch and images_u8.is_cuda and images_u8.size(0) <= self.graph_max_batch \
-                    and not self.has_trainable_stage:
-                g = self._graph_for(images_u8, sizes, pixel_mean, pixel_std)
-                if g is not None:
-                    return g(images_u8)
-            return self._forward_uint8(images_u8, sizes, pixel_mean, pixel_std)
-
-    # ---- the frozen forward as a HIP graph (small batches: the ~25 launches of the backbone cost more host time than
-    # device time; one replay instead).  Opt-in (`graph_max_batch`, set by the overlapped trainer): the returned maps
-    # are the graph's static buffers, valid until the next call with the same input shape ----
-    graph_max_batch = 0
-    GRAPH_CACHE = 4  # graphs kept (each holds the backbone's activations of its shape)
-    GRAPH_AFTER = 3  # calls with a shape before it is captured
-
-    def _graph_fingerprint(self):
-        ps = getattr(self, "_graph_tensors", None)
-        if ps is None:
-            ps = self._graph_tensors = list(self.parameters()) + list(self.buffers())
-        return sum(t._version for t in ps), ps[0].data_ptr() if ps else 0
-
-    def _graph_for(self, images_u8, sizes, pixel_mean, pixel_std):
-        from .._lib import PROFILING
-
-        if PROFILING[0] or torch.cuda.is_current_stream_capturing():
-            return None
-        fp = self._graph_fingerprint()
-        cache = self.__dict__.setdefault("_graphs", {})
-        if any(v and v.fingerprint != fp for v in cache.values()):
-            cache.clear()  # a weight changed (load_state_dict, broadcast): the folded copies the graphs point at are stale
-        key = (tuple(images_u8.shape), sizes.data_ptr(), tuple(pixel_mean), tuple(pixel_std), H.x3_active(), H.mx_active())
-        g = cache.get(key)
-        if g is None:
-            # capture on the third call with a shape: with multi-scale inputs most shapes never repeat, and a capture
-            # costs three forwards
-            seen = self.__dict__.setdefault("_graph_seen", {})
-            if len(seen) > 64:
-                seen.clear()
-            seen[key] = seen.get(key, 0) + 1
-            if seen[key] < self.GRAPH_AFTER:
-                return None
-            if len(cache) >= self.GRAPH_CACHE:
-                cache.pop(next(iter(cache)))
-            try:
-                g = _BackboneGraph(self, images_u8, sizes, pixel_mean, pixel_std, fp)
-            except Exception as e:  # noqa: BLE001 -- out of memory in the graph's pool, an API call refused under capture
-                import warnings
-
-                warnings.warn(f"wsovod_amd: HIP graph capture of the frozen backbone failed for input shape "
-                              f"{tuple(images_u8.shape)} ({type(e).__name__}: {e}); this shape keeps the eager launches")
-                g = False  # remembered: never retried for this key
-            cache[key] = g
-        return g or None
-
     def _stem_conv1(self, images_u8, sizes, pixel_mean, pixel_std):
         """relu(conv1 (normalised image)) as the stem's forward produces it."""
         stem = self.stem
@@ -896,10 +907,6 @@ class ResNet(nn.Module):
             with torch.no_grad():
                 xs = self._stem_uint8(images_u8, sizes, pixel_mean, pixel_std)
         return self._run(xs)
-
-    def output_shape(self):
-        return {name: ShapeSpec(channels=self._out_feature_channels[name], stride=self._out_feature_strides[name])
-                for name in self._out_features}
 
     def freeze(self, freeze_at=0):
         if freeze_at >= 1:

@@ -246,6 +246,10 @@ class WSOVODRPN_V2(nn.Module):
     @classmethod
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):
         in_features = cfg.MODEL.RPN.IN_FEATURES
+        missing = [f for f in in_features if f not in input_shape]
+        if missing:  # (the reference's V_16 YAML keeps its base's ["res5"], which a VGG backbone does not produce)
+            raise KeyError(f"MODEL.RPN.IN_FEATURES = {list(in_features)} names {missing}, which the backbone "
+                           f"{cfg.MODEL.BACKBONE.NAME} does not return; available features: {sorted(input_shape)}")
         shapes = [input_shape[f] for f in in_features]
         return {
             "in_features": in_features,

@@ -12,15 +12,20 @@ _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs"
 
 
 def hot_path_cfg(depth=18, K=20, D=512, precision="bf16", pooler="ROIPool", device="cuda", weight_path=None,
-                 emb_seed=7, rpn=False, freeze_at=None):
+                 emb_seed=7, rpn=False, freeze_at=None, backbone="resnet"):
     """WSOVOD_WSR_{18,50}_DC5_1x in proposals-only mode: the keys below are the values of
     /root/reference/configs/PascalVOC-Detection/{Base-RCNN-DilatedC5,WSOVOD_WSR_18_DC5_1x}.yaml
-    that the hot path reads, with PROPOSAL_GENERATOR=PrecomputedProposals, BBOX_REFINE off."""
+    that the hot path reads, with PROPOSAL_GENERATOR=PrecomputedProposals, BBOX_REFINE off.
+    backbone="vgg16": WSOVOD_V_16_DC5_1x instead (hot_path_vgg16.yaml; `depth` is not read)."""
     cfg = get_cfg()
-    cfg.merge_from_file(os.path.join(_CONFIG_DIR, f"hot_path_wsr{depth}.yaml"))
-    if rpn:  # the shipped form: RPN boxes next to the loaded proposals (SURVEY 8f n1)
-        assert depth == 18
-        cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_wsr18_rpn.yaml"))
+    if backbone == "vgg16":
+        cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_rpn.yaml" if rpn else "hot_path_vgg16.yaml"))
+    else:
+        assert backbone == "resnet", backbone
+        cfg.merge_from_file(os.path.join(_CONFIG_DIR, f"hot_path_wsr{depth}.yaml"))
+        if rpn:  # the shipped form: RPN boxes next to the loaded proposals (SURVEY 8f n1)
+            assert depth == 18
+            cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_wsr18_rpn.yaml"))
     if weight_path is None:
         weight_path = os.path.join(tempfile.mkdtemp(prefix="wsovod_emb_"), f"emb_{K}x{D}.pkl")
         with open(weight_path, "wb") as f:
@@ -65,7 +70,8 @@ def build_hot_path_model(seed=0, calibrate_synthetic=True, **kw):
     """Random-init model of the named architecture (reference initialisers).  With
     `calibrate_synthetic` the frozen stem's first FrozenBN scale is set to 1/64 so that the random
     backbone maps raw-scale pixels (PIXEL_STD = 1: inputs of +-128) to O(1) features, as a trained
-    checkpoint would; it changes no arithmetic, only keeps synthetic training finite."""
+    checkpoint would; it changes no arithmetic, only keeps synthetic training finite.  backbone="vgg16" has no norm to
+    carry the scale: conv1_1's weight itself is multiplied by 1/64."""
     from .modeling import build_model
 
     cfg = hot_path_cfg(**kw)
@@ -73,7 +79,10 @@ def build_hot_path_model(seed=0, calibrate_synthetic=True, **kw):
     model = build_model(cfg)
     if calibrate_synthetic:
         with torch.no_grad():
-            model.backbone.stem.conv1.norm.weight.fill_(1.0 / 64.0)
+            if kw.get("backbone", "resnet") == "vgg16":
+                model.backbone.plain1[0].conv1.weight.mul_(1.0 / 64.0)
+            else:
+                model.backbone.stem.conv1.norm.weight.fill_(1.0 / 64.0)
     return cfg, model
 
 

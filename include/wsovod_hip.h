@@ -139,6 +139,21 @@ int wsovod_roi_pool_forward_m2(const void* feat, int dtype, int layout, const fl
 int wsovod_roi_loop_pool_forward(const void* feat, int dtype, int layout, const float* rois, int R, int N, int C, int H,
                                  int W, int ph, int pw, float spatial_scale, float context_ratio, float* out,
                                  int* argmax, wsovod_stream_t stream);
+/* The same pool FUSED with what the reference does to its output before the first FC layer (wsovod/modeling/roi_heads.py:
+ * 727-739: `box_features * (objectness_logits + 1)` over the pooled (3R, C, ph, pw) tensor, then the neck's input cast),
+ * with the argument rules of wsovod_roi_pool_forward_ws.  roi_scale: (R) fp32 or NULL -- row r of ALL THREE parts is
+ * multiplied by roi_scale[r] in fp32 before it is encoded (no repeated scale vector exists).  out_dtype: WSOVOD_F32,
+ * WSOVOD_BF16, WSOVOD_BF16X2, WSOVOD_BF16X2P (planar: the hi plane of all 3R rows, then the lo plane) or WSOVOD_F16MX (unit
+ * scale); the 3R x (C ph pw) matrix is byte for byte what the plain pool's encoders write for the same fp32 values.
+ * out_hi (may be NULL; bf16x2 / f16mx outputs): the plain bf16 rounding, the operand of the first FC layer's weight
+ * gradient.  The bf16x2 / f16mx forms need pw = 7, ph <= 16, C a multiple of 256 and 16-byte aligned outputs; a map that
+ * is not NHWC or a shape outside these rules is WSOVOD_ERR_INVALID_ARGUMENT, never another kernel.  argmax may be NULL
+ * (frozen backbone: nobody reads it): the kernel then keeps no index accumulators and no index tiles in LDS.  The pooling
+ * arithmetic -- rectangles, bins, accumulators from 0, first maximum, -1 for an empty bin -- is the entry's above. */
+int wsovod_roi_loop_pool_forward_ex(const void* feat, int dtype, int layout, const float* rois, const float* roi_scale,
+                                    int R, int N, int C, int H, int W, int ph, int pw, float spatial_scale,
+                                    float context_ratio, void* out, int out_dtype, int* argmax, void* out_hi,
+                                    wsovod_stream_t stream);
 
 /* grad_in (N,C,H,W) in `layout`, fp32, must be zero-filled by the caller; scatter-add
  * through argmax (ROILoopPool_cpu.cpp:82-123).  grad_out is (R,C,ph,pw) contiguous fp32. */

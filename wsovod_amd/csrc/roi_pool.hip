@@ -329,6 +329,88 @@ __device__ __forceinline__ float hw_max3(float a, float b, float c) {
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// The fp32 [channel][bin] LDS tile of one workgroup leaves as the contiguous run [obase, obase + nvalid) of the pooled
+// (rows, C, PH, PW) tensor, encoded as `out_dtype` asks (shared by the RoIPool rows kernel and the three-output pool).
+__device__ __forceinline__ void flush_pooled_tile(const float* sval, int nvalid, long long obase, void* out, int out_dtype,
+                                                  void* out_hi, int tid, int nthreads) {
+  const bool vec = (nvalid & 3) == 0 && (obase & 3) == 0;
+  if (out_dtype == WSOVOD_F32) {
+    float* o = (float*)out + obase;
+    if (vec)
+      for (int i = tid * 4; i < nvalid; i += nthreads * 4) *(float4*)(o + i) = *(const float4*)(sval + i);
+    else
+      for (int i = tid; i < nvalid; i += nthreads) o[i] = sval[i];
+  } else if (out_dtype == WSOVOD_F16MX) {
+    // unit-scale f16mx (include/wsovod_hip.h, round 6): 8 values per lane = 16 B of fp16 hi + 8 B of e4m3 q + 8 B of e4m3 ql of
+    // one 128-byte group, and -- `out_hi` -- the plain bf16 rounding, the operand of the first FC layer's weight gradient
+    char* o = (char*)out;
+    for (int i = tid * 8; i < nvalid; i += nthreads * 8) {
+      wsovod_mx::f16x4 h0, h1;
+      int q0, q1, l0, l1;
+      const f32x4 v0 = *(const f32x4*)(sval + i), v1 = *(const f32x4*)(sval + i + 4);
+      wsovod_mx::mx_enc4_unit(v0, h0, q0, l0);
+      wsovod_mx::mx_enc4_unit(v1, h1, q1, l1);
+      const long long k = obase + i;
+      char* d = o + wsovod_mx::mx_group(k);
+      const int w = (int)(k & 31);
+      __builtin_nontemporal_store(wsovod_mx::f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]}, (wsovod_mx::f16x8*)(d + 2 * w));
+      __builtin_nontemporal_store(wsovod_mx::i32x2{q0, q1}, (wsovod_mx::i32x2*)(d + 64 + w));
+      __builtin_nontemporal_store(wsovod_mx::i32x2{l0, l1}, (wsovod_mx::i32x2*)(d + 96 + w));
+      if (out_hi)
+        __builtin_nontemporal_store(bf16x8{(bf16_t)v0[0], (bf16_t)v0[1], (bf16_t)v0[2], (bf16_t)v0[3], (bf16_t)v1[0], (bf16_t)v1[1],
+                                           (bf16_t)v1[2], (bf16_t)v1[3]}, (bf16x8*)((bf16_t*)out_hi + k));
+    }
+  } else if (out_dtype == WSOVOD_BF16X2 || out_dtype == WSOVOD_BF16X2P) {
+    // bf16x2 (include/wsovod_hip.h): the run [obase, obase + nvalid) covers whole 32-value groups (launcher); 8 values per
+    // lane = 16 B of hi and 16 B of lo half a line further, streamed past L2 like the bf16 form.  PLANAR (round 5): hi to the
+    // first bf16 matrix of the output, lo to the second (`out_hi` = its base, set by the launcher): the hi plane is at once
+    // the plain bf16 operand of the first FC layer's weight gradient -- no third store per value
+    bf16_t* o = (bf16_t*)out;
+    const bool planar = out_dtype == WSOVOD_BF16X2P;
+    for (int i = tid * 8; i < nvalid; i += nthreads * 8) {
+      const f32x4 q0 = *(const f32x4*)(sval + i), q1 = *(const f32x4*)(sval + i + 4);
+      bf16x8 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        hi[e] = (bf16_t)q0[e];
+        hi[4 + e] = (bf16_t)q1[e];
+        const float h0 = (float)hi[e], h1 = (float)hi[4 + e];
+        lo[e] = (bf16_t)(__builtin_isinf(h0) ? 0.f : q0[e] - h0);
+        lo[4 + e] = (bf16_t)(__builtin_isinf(h1) ? 0.f : q1[e] - h1);
+      }
+      const long long k = obase + i;
+      if (planar) {
+        __builtin_nontemporal_store(hi, (bf16x8*)(o + k));
+        __builtin_nontemporal_store(lo, (bf16x8*)((bf16_t*)out_hi + k));
+        continue;
+      }
+      bf16_t* d = o + ((k >> 5) << 6) + (k & 31);
+      __builtin_nontemporal_store(hi, (bf16x8*)d);
+      __builtin_nontemporal_store(lo, (bf16x8*)(d + 32));
+      if (out_hi) __builtin_nontemporal_store(hi, (bf16x8*)((bf16_t*)out_hi + k));  // plain bf16 copy (see the launcher)
+    }
+  } else {
+    bf16_t* o = (bf16_t*)out + obase;
+    if (vec && (nvalid & 7) == 0 && (obase & 7) == 0)
+      for (int i = tid * 8; i < nvalid; i += nthreads * 8) {
+        const f32x4 q0 = *(const f32x4*)(sval + i), q1 = *(const f32x4*)(sval + i + 4);
+        const bf16x8 pk = {(bf16_t)q0[0], (bf16_t)q0[1], (bf16_t)q0[2], (bf16_t)q0[3],
+                           (bf16_t)q1[0], (bf16_t)q1[1], (bf16_t)q1[2], (bf16_t)q1[3]};
+        // 16 bytes per lane, non-temporal: the pooled tensor (822 MB at 32 images) is written once and read by the
+        // next kernel; it must not evict the feature map the neighbouring rois re-read from L2 (0.896 -> 0.832 ms)
+        __builtin_nontemporal_store(pk, (bf16x8*)(o + i));
+      }
+    else if (vec)
+      for (int i = tid * 4; i < nvalid; i += nthreads * 4) {
+        const float4 q = *(const float4*)(sval + i);
+        bf16x4 pk = {(bf16_t)q.x, (bf16_t)q.y, (bf16_t)q.z, (bf16_t)q.w};
+        *(bf16x4*)(o + i) = pk;
+      }
+    else
+      for (int i = tid; i < nvalid; i += nthreads) o[i] = (bf16_t)sval[i];
+  }
+}
+
 template <typename T, bool ARGMAX, int PWT, int CPL, bool OBF = false>
 __global__ void roi_pool_fwd_nhwc_rows(const T* __restrict__ feat, const float* __restrict__ rois,
                                        const float* __restrict__ roi_scale, int C, int H, int W, int PH,
@@ -496,80 +578,8 @@ __global__ void roi_pool_fwd_nhwc_rows(const T* __restrict__ feat, const float* 
     else
       for (int i = tid; i < nvalid; i += nthreads) o[i] = sval[i];
     return;
-  } else if (out_dtype == WSOVOD_F32) {
-    float* o = (float*)out + obase;
-    if (vec)
-      for (int i = tid * 4; i < nvalid; i += nthreads * 4) *(float4*)(o + i) = *(const float4*)(sval + i);
-    else
-      for (int i = tid; i < nvalid; i += nthreads) o[i] = sval[i];
-  } else if (out_dtype == WSOVOD_F16MX) {
-    // unit-scale f16mx (include/wsovod_hip.h, round 6): 8 values per lane = 16 B of fp16 hi + 8 B of e4m3 q + 8 B of e4m3 ql of
-    // one 128-byte group, and -- `out_hi` -- the plain bf16 rounding, the operand of the first FC layer's weight gradient
-    char* o = (char*)out;
-    for (int i = tid * 8; i < nvalid; i += nthreads * 8) {
-      wsovod_mx::f16x4 h0, h1;
-      int q0, q1, l0, l1;
-      const f32x4 v0 = *(const f32x4*)(sval + i), v1 = *(const f32x4*)(sval + i + 4);
-      wsovod_mx::mx_enc4_unit(v0, h0, q0, l0);
-      wsovod_mx::mx_enc4_unit(v1, h1, q1, l1);
-      const long long k = obase + i;
-      char* d = o + wsovod_mx::mx_group(k);
-      const int w = (int)(k & 31);
-      __builtin_nontemporal_store(wsovod_mx::f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]}, (wsovod_mx::f16x8*)(d + 2 * w));
-      __builtin_nontemporal_store(wsovod_mx::i32x2{q0, q1}, (wsovod_mx::i32x2*)(d + 64 + w));
-      __builtin_nontemporal_store(wsovod_mx::i32x2{l0, l1}, (wsovod_mx::i32x2*)(d + 96 + w));
-      if (out_hi)
-        __builtin_nontemporal_store(bf16x8{(bf16_t)v0[0], (bf16_t)v0[1], (bf16_t)v0[2], (bf16_t)v0[3], (bf16_t)v1[0], (bf16_t)v1[1],
-                                           (bf16_t)v1[2], (bf16_t)v1[3]}, (bf16x8*)((bf16_t*)out_hi + k));
-    }
-  } else if (out_dtype == WSOVOD_BF16X2 || out_dtype == WSOVOD_BF16X2P) {
-    // bf16x2 (include/wsovod_hip.h): the run [obase, obase + nvalid) covers whole 32-value groups (launcher); 8 values per
-    // lane = 16 B of hi and 16 B of lo half a line further, streamed past L2 like the bf16 form.  PLANAR (round 5): hi to the
-    // first bf16 matrix of the output, lo to the second (`out_hi` = its base, set by the launcher): the hi plane is at once
-    // the plain bf16 operand of the first FC layer's weight gradient -- no third store per value
-    bf16_t* o = (bf16_t*)out;
-    const bool planar = out_dtype == WSOVOD_BF16X2P;
-    for (int i = tid * 8; i < nvalid; i += nthreads * 8) {
-      const f32x4 q0 = *(const f32x4*)(sval + i), q1 = *(const f32x4*)(sval + i + 4);
-      bf16x8 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (bf16_t)q0[e];
-        hi[4 + e] = (bf16_t)q1[e];
-        const float h0 = (float)hi[e], h1 = (float)hi[4 + e];
-        lo[e] = (bf16_t)(__builtin_isinf(h0) ? 0.f : q0[e] - h0);
-        lo[4 + e] = (bf16_t)(__builtin_isinf(h1) ? 0.f : q1[e] - h1);
-      }
-      const long long k = obase + i;
-      if (planar) {
-        __builtin_nontemporal_store(hi, (bf16x8*)(o + k));
-        __builtin_nontemporal_store(lo, (bf16x8*)((bf16_t*)out_hi + k));
-        continue;
-      }
-      bf16_t* d = o + ((k >> 5) << 6) + (k & 31);
-      __builtin_nontemporal_store(hi, (bf16x8*)d);
-      __builtin_nontemporal_store(lo, (bf16x8*)(d + 32));
-      if (out_hi) __builtin_nontemporal_store(hi, (bf16x8*)((bf16_t*)out_hi + k));  // plain bf16 copy (see the launcher)
-    }
   } else {
-    bf16_t* o = (bf16_t*)out + obase;
-    if (vec && (nvalid & 7) == 0 && (obase & 7) == 0)
-      for (int i = tid * 8; i < nvalid; i += nthreads * 8) {
-        const f32x4 q0 = *(const f32x4*)(sval + i), q1 = *(const f32x4*)(sval + i + 4);
-        const bf16x8 pk = {(bf16_t)q0[0], (bf16_t)q0[1], (bf16_t)q0[2], (bf16_t)q0[3],
-                           (bf16_t)q1[0], (bf16_t)q1[1], (bf16_t)q1[2], (bf16_t)q1[3]};
-        // 16 bytes per lane, non-temporal: the pooled tensor (822 MB at 32 images) is written once and read by the
-        // next kernel; it must not evict the feature map the neighbouring rois re-read from L2 (0.896 -> 0.832 ms)
-        __builtin_nontemporal_store(pk, (bf16x8*)(o + i));
-      }
-    else if (vec)
-      for (int i = tid * 4; i < nvalid; i += nthreads * 4) {
-        const float4 q = *(const float4*)(sval + i);
-        bf16x4 pk = {(bf16_t)q.x, (bf16_t)q.y, (bf16_t)q.z, (bf16_t)q.w};
-        *(bf16x4*)(o + i) = pk;
-      }
-    else
-      for (int i = tid; i < nvalid; i += nthreads) o[i] = (bf16_t)sval[i];
+    flush_pooled_tile((const float*)sval, nvalid, obase, out, out_dtype, out_hi, tid, nthreads);
   }
   if (ARGMAX) {
     int* o = argmax + obase;
@@ -666,11 +676,14 @@ __device__ __forceinline__ LoopRects loop_rects(const float* roi, float spatial_
 
 // One pooled row `ph` of the bins of the rectangle (sw, sh, ew, eh), pooled columns [pw0, pw0 + npw): the cells of a bin
 // strictly inside (hw0, hh0, hw1, hh1) are skipped by accumulator B (and by accumulator A too when SKIP_A); results go to
-// the [channel][bin] LDS tiles.  TWO = both accumulators wanted (region + frame), else only B (context).
-template <typename T, int PWT, int CPL, bool TWO>
+// the [channel][bin] LDS tiles.  TWO = both accumulators wanted (region + frame), else only B (context).  ARGMAX = false:
+// values only -- no index accumulators, no index tiles (sargA / sargB are not touched).  `scaled`: the maxima are multiplied
+// by `scale` (the roi's objectness + 1, roi_heads.py:733-739 of the reference) on their way into the tile.
+template <typename T, int PWT, int CPL, bool TWO, bool ARGMAX>
 __device__ __forceinline__ void loop_pool_row(const T* __restrict__ base, int C, int H, int W, int PH, int PW, int ph,
                                               int pw0, int npw, int sw, int sh, int ew, int eh, int hw0, int hh0, int hw1,
-                                              int hh1, int lane, float* svalA, int* sargA, float* svalB, int* sargB) {
+                                              int hh1, int lane, float* svalA, int* sargA, float* svalB, int* sargB,
+                                              float scale, bool scaled) {
   typedef T vecc __attribute__((ext_vector_type(CPL)));
   const int roi_w = max(ew - sw + 1, 1), roi_h = max(eh - sh + 1, 1);
   const float bin_h = (float)roi_h / (float)PH, bin_w = (float)roi_w / (float)PW;
@@ -708,11 +721,11 @@ __device__ __forceinline__ void loop_pool_row(const T* __restrict__ base, int C,
             const float vq = to_f32(v[k][q]);
             if (TWO && vq > mvA[k][q]) {
               mvA[k][q] = vq;
-              miA[k][q] = h * W + w;
+              if (ARGMAX) miA[k][q] = h * W + w;
             }
             if (!hole && vq > mvB[k][q]) {
               mvB[k][q] = vq;
-              miB[k][q] = h * W + w;
+              if (ARGMAX) miB[k][q] = h * W + w;
             }
           }
         }
@@ -727,51 +740,55 @@ __device__ __forceinline__ void loop_pool_row(const T* __restrict__ base, int C,
       for (int q = 0; q < CPL; ++q) {
         const int o = (lane * CPL + q) * nbins + ph * PW + pw0 + k;
         if (TWO && svalA) {
-          svalA[o] = mvA[k][q];
-          sargA[o] = miA[k][q];
+          svalA[o] = scaled ? mvA[k][q] * scale : mvA[k][q];
+          if (ARGMAX) sargA[o] = miA[k][q];
         }
         if (svalB) {
-          svalB[o] = mvB[k][q];
-          sargB[o] = miB[k][q];
+          svalB[o] = scaled ? mvB[k][q] * scale : mvB[k][q];
+          if (ARGMAX) sargB[o] = miB[k][q];
         }
       }
     }
 }
 
-template <typename T, int CPL>
-__global__ void roi_loop_pool_fwd_nhwc_rows(const T* __restrict__ feat, const float* __restrict__ rois, int R, int C,
-                                            int H, int W, int PH, int PW, float spatial_scale, float context_ratio,
-                                            float* __restrict__ out, int* __restrict__ argmax, int cgroups, int share) {
+// One kernel for both C entries.  wsovod_roi_loop_pool_forward: ARGMAX, fp32 out, no scale.  wsovod_roi_loop_pool_forward_ex:
+// the fused form -- row r of all three parts times roi_scale[r] in fp32, then the output encoders of the plain pool
+// (flush_pooled_tile: fp32 / bf16 / bf16x2 interleaved or planar / unit-scale f16mx, + the plain bf16 copy `out_hi`), over
+// the 3R x (C PH PW) matrix; without ARGMAX the LDS holds value tiles only (half the bytes per tile).
+template <typename T, int CPL, bool ARGMAX>
+__global__ void roi_loop_pool_fwd_nhwc_rows(const T* __restrict__ feat, const float* __restrict__ rois,
+                                            const float* __restrict__ roi_scale, int R, int C, int H, int W, int PH, int PW,
+                                            float spatial_scale, float context_ratio, void* out, int out_dtype, void* out_hi,
+                                            int* __restrict__ argmax, int cgroups, int share) {
   constexpr int PWT = 7, CG = 64 * CPL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int nbins = PH * PW;
-  float* svalA = (float*)smem;  // tile A: region, later context; tile B: frame
-  int* sargA = (int*)(svalA + CG * nbins);
-  float* svalB = (float*)(sargA + CG * nbins);
-  int* sargB = (int*)(svalB + CG * nbins);
+  const int tile = CG * nbins;  // elements of one [channel][bin] tile
+  // tile A: region, later context; tile B: frame.  ARGMAX: [valA | argA | valB | argB], else [valA | valB]
+  float* svalA = (float*)smem;
+  int* sargA = ARGMAX ? (int*)(svalA + tile) : nullptr;
+  float* svalB = svalA + (ARGMAX ? 2 : 1) * tile;
+  int* sargB = ARGMAX ? (int*)(svalB + tile) : nullptr;
   const int r = blockIdx.x / cgroups;
   const int c0 = (blockIdx.x - r * cgroups) * CG;
   const int c = c0 + lane * CPL;
   const LoopRects q = loop_rects(rois + (long long)r * 5, spatial_scale, context_ratio, H, W);
+  const bool scaled = roi_scale != nullptr;
+  const float scale = scaled ? roi_scale[r] : 1.0f;
   const T* base = feat + (long long)q.batch * H * W * C + (c + CPL <= C ? c : 0);  // (lanes past C read channel 0, never stored)
   const long long part = (long long)R * C * nbins;
   const int nvalid = min(CG, C - c0) * nbins;
   const long long obase = ((long long)r * C + c0) * nbins;
   const bool vec = (nvalid & 3) == 0 && (obase & 3) == 0;
   auto flush = [&](const float* sv, const int* sa, long long off) {
-    float* o = out + off + obase;
-    int* oa = argmax + off + obase;
-    if (vec) {
-      for (int i = threadIdx.x * 4; i < nvalid; i += blockDim.x * 4) {
-        *(float4*)(o + i) = *(const float4*)(sv + i);
-        *(int4*)(oa + i) = *(const int4*)(sa + i);
-      }
-    } else {
-      for (int i = threadIdx.x; i < nvalid; i += blockDim.x) {
-        o[i] = sv[i];
-        oa[i] = sa[i];
-      }
+    flush_pooled_tile(sv, nvalid, off + obase, out, out_dtype, out_hi, threadIdx.x, blockDim.x);
+    if constexpr (ARGMAX) {
+      int* oa = argmax + off + obase;
+      if (vec)
+        for (int i = threadIdx.x * 4; i < nvalid; i += blockDim.x * 4) *(int4*)(oa + i) = *(const int4*)(sa + i);
+      else
+        for (int i = threadIdx.x; i < nvalid; i += blockDim.x) oa[i] = sa[i];
     }
   };
   // region + frame: one scan of the roi's own bins feeds both (frame skips the cells strictly inside the shrunk roi).
@@ -779,8 +796,8 @@ __global__ void roi_loop_pool_fwd_nhwc_rows(const T* __restrict__ feat, const fl
   if (!share) svalB = nullptr, sargB = nullptr;
   for (int ph = wave; ph < PH; ph += nwaves)
     for (int pw0 = 0; pw0 < PW; pw0 += PWT)
-      loop_pool_row<T, PWT, CPL, true>(base, C, H, W, PH, PW, ph, pw0, min(PWT, PW - pw0), q.sw, q.sh, q.ew, q.eh, q.swi,
-                                       q.shi, q.ewi, q.ehi, lane, svalA, sargA, svalB, sargB);
+      loop_pool_row<T, PWT, CPL, true, ARGMAX>(base, C, H, W, PH, PW, ph, pw0, min(PWT, PW - pw0), q.sw, q.sh, q.ew, q.eh,
+                                               q.swi, q.shi, q.ewi, q.ehi, lane, svalA, sargA, svalB, sargB, scale, scaled);
   __syncthreads();
   flush(svalA, sargA, 0);
   if (share) {
@@ -789,8 +806,9 @@ __global__ void roi_loop_pool_fwd_nhwc_rows(const T* __restrict__ feat, const fl
     __syncthreads();
     for (int ph = wave; ph < PH; ph += nwaves)
       for (int pw0 = 0; pw0 < PW; pw0 += PWT)
-        loop_pool_row<T, PWT, CPL, false>(base, C, H, W, PH, PW, ph, pw0, min(PWT, PW - pw0), q.sw, q.sh, q.ew, q.eh, q.swi,
-                                          q.shi, q.ewi, q.ehi, lane, nullptr, nullptr, svalA, sargA);
+        loop_pool_row<T, PWT, CPL, false, ARGMAX>(base, C, H, W, PH, PW, ph, pw0, min(PWT, PW - pw0), q.sw, q.sh, q.ew, q.eh,
+                                                  q.swi, q.shi, q.ewi, q.ehi, lane, nullptr, nullptr, svalA, sargA, scale,
+                                                  scaled);
     __syncthreads();
     flush(svalA, sargA, part);
   }
@@ -798,8 +816,9 @@ __global__ void roi_loop_pool_fwd_nhwc_rows(const T* __restrict__ feat, const fl
   // context: the bins of the grown roi without the cells strictly inside the roi itself
   for (int ph = wave; ph < PH; ph += nwaves)
     for (int pw0 = 0; pw0 < PW; pw0 += PWT)
-      loop_pool_row<T, PWT, CPL, false>(base, C, H, W, PH, PW, ph, pw0, min(PWT, PW - pw0), q.swo, q.sho, q.ewo, q.eho,
-                                        q.sw, q.sh, q.ew, q.eh, lane, nullptr, nullptr, svalA, sargA);
+      loop_pool_row<T, PWT, CPL, false, ARGMAX>(base, C, H, W, PH, PW, ph, pw0, min(PWT, PW - pw0), q.swo, q.sho, q.ewo,
+                                                q.eho, q.sw, q.sh, q.ew, q.eh, lane, nullptr, nullptr, svalA, sargA, scale,
+                                                scaled);
   __syncthreads();
   flush(svalA, sargA, 2 * part);
 }
@@ -1587,54 +1606,96 @@ static int roi_pool_forward_impl(const void* feat, int dtype, int layout, const 
   return WSOVOD_OK;
 }
 
-int wsovod_roi_loop_pool_forward(const void* feat, int dtype, int layout, const float* rois, int R, int N, int C, int H,
-                                 int W, int ph, int pw, float spatial_scale, float context_ratio, float* out,
-                                 int* argmax, wsovod_stream_t stream) {
+// Both ROILoopPool entries.  `ex`: the fused form (argument rules of wsovod_roi_pool_forward_ws); else the reference's op.
+static int roi_loop_pool_forward_impl(bool ex, const void* feat, int dtype, int layout, const float* rois,
+                                      const float* roi_scale, int R, int N, int C, int H, int W, int ph, int pw,
+                                      float spatial_scale, float context_ratio, void* out, int out_dtype, int* argmax,
+                                      void* out_hi, wsovod_stream_t stream) {
   WS_CHECK_ARG(layout == WSOVOD_NCHW || layout == WSOVOD_NHWC, "wsovod_roi_loop_pool_forward: bad layout");
   WS_CHECK_ARG(dtype == WSOVOD_F32 || dtype == WSOVOD_BF16, "wsovod_roi_loop_pool_forward: bad dtype");
   WS_CHECK_ARG(R >= 0 && N >= 0 && C > 0 && H > 0 && W > 0 && ph > 0 && pw > 0 && context_ratio > 0.f,
                "wsovod_roi_loop_pool_forward: bad shape");
   WS_CHECK_ARG((long long)H * W < (1ll << 31), "wsovod_roi_loop_pool_forward: H*W overflows int32 argmax");
+  const int nbins = ph * pw;
+  const bool carrier_out = out_dtype == WSOVOD_BF16X2 || out_dtype == WSOVOD_BF16X2P || out_dtype == WSOVOD_F16MX;
+  if (ex) {
+    WS_CHECK_ARG(out_dtype == WSOVOD_F32 || out_dtype == WSOVOD_BF16 || carrier_out, "wsovod_roi_loop_pool_forward_ex: bad out_dtype");
+    WS_CHECK_ARG(layout == WSOVOD_NHWC, "wsovod_roi_loop_pool_forward_ex: the feature map must be NHWC (channels_last)");
+    WS_CHECK_ARG((long long)3 * R * C * nbins < (1ll << 40), "wsovod_roi_loop_pool_forward_ex: output too large");
+    WS_CHECK_ARG(!out_hi || ((out_dtype == WSOVOD_BF16X2 || out_dtype == WSOVOD_F16MX) && ((uintptr_t)out_hi & 15) == 0),
+                 "wsovod_roi_loop_pool_forward_ex: the bf16 copy goes with a bf16x2 / f16mx output");
+    // bf16x2 / f16mx output: every workgroup's run of outputs is whole 32-value groups, written 8 values per lane
+    WS_CHECK_ARG(!carrier_out || (pw == 7 && ph <= 16 && C % 256 == 0 && ((uintptr_t)feat & 7) == 0 && ((uintptr_t)out & 15) == 0),
+                 "wsovod_roi_loop_pool_forward_ex: bf16x2 / f16mx output needs NHWC, pw = 7, ph <= 16, C a multiple of 256");
+    if (out_dtype == WSOVOD_BF16X2P) {  // lo plane of all 3R rows behind the hi plane
+      WS_CHECK_ARG(((long long)3 * R * C * nbins) % 8 == 0, "wsovod_roi_loop_pool_forward_ex: planar bf16x2 output needs 16-byte aligned planes");
+      out_hi = (char*)out + (long long)3 * R * C * nbins * 2;
+    }
+  }
   if (R == 0) return WSOVOD_OK;
-  WS_CHECK_ARG(feat && rois && out && argmax, "wsovod_roi_loop_pool_forward: null pointer");
+  WS_CHECK_ARG(feat && rois && out && (ex || argmax), "wsovod_roi_loop_pool_forward: null pointer");
   if (layout != WSOVOD_NHWC) {
     // channels per lane need the channels innermost: the HIP backbone's layout.  The reference's NCHW tensors go through
     // `.contiguous(memory_format=torch.channels_last)` in the Python fronts (wsovod_amd/_C.py, layers/hip_ops.py).
     wsovod::set_error("wsovod_roi_loop_pool_forward: the feature map must be NHWC (channels_last)");
     return WSOVOD_ERR_UNSUPPORTED;
   }
-  static int slot = wsovod::prof_slot("roi_loop_pool_fwd");
+  static int slot = wsovod::prof_slot("roi_loop_pool_fwd"), slot_ex = wsovod::prof_slot("roi_loop_pool_fwd_ex");
   hipStream_t s = (hipStream_t)stream;
-  const int nbins = ph * pw;
-  // two (channels, bins) value + argmax tiles per workgroup; 2 channels per lane when both fit next to a second workgroup
-  const bool two = (C & 1) == 0 && (((uintptr_t)feat) & 7) == 0 && C >= 128 && 2 * 128 * nbins * 8 <= 80 * 1024;
+  // two (channels, bins) tiles per workgroup -- value + argmax (8 bytes per bin), or values only (4: twice the channels or
+  // twice the workgroups in the same LDS); 2 channels per lane when both fit next to a second workgroup
+  const int be = argmax ? 8 : 4;
+  const bool two = (C & 1) == 0 && (((uintptr_t)feat) & 7) == 0 && C >= 128 && 2 * 128 * nbins * be <= 80 * 1024;
   const int cpl = two ? 2 : 1, cg = 64 * cpl;
-  const int share = 2 * cg * nbins * 8 <= 160 * 1024 ? 1 : 0;  // region and frame from one scan (two tiles) or from two
-  const int lds = (share ? 2 : 1) * cg * nbins * 8;
+  const int share = 2 * cg * nbins * be <= 160 * 1024 ? 1 : 0;  // region and frame from one scan (two tiles) or from two
+  const int lds = (share ? 2 : 1) * cg * nbins * be;
   if (lds > 160 * 1024) {
     wsovod::set_error("wsovod_roi_loop_pool_forward: a %d x %d pooled tile of 64 channels does not fit the LDS", ph, pw);
     return WSOVOD_ERR_UNSUPPORTED;
   }
   const int cgroups = ceil_div(C, cg);
+  WS_CHECK_ARG((long long)R * cgroups < (1ll << 31), "wsovod_roi_loop_pool_forward: too many workgroups");
   const int nwaves = std::min(ph, 8);
   const double cells = (double)R * C * nbins;
-  wsovod::ProfScope prof(slot, s, 0.0, cells * 24.0 + (double)N * C * H * W * (dtype == WSOVOD_BF16 ? 2 : 4));
-#define LAUNCH_LOOP(T, CPL)                                                                                          \
+  const double obytes = out_dtype == WSOVOD_BF16 ? 2.0 : 4.0;
+  wsovod::ProfScope prof(ex ? slot_ex : slot, s, 0.0,
+                         cells * 3.0 * (obytes + (argmax ? 4.0 : 0.0) + (out_hi && out_dtype != WSOVOD_BF16X2P ? 2.0 : 0.0)) +
+                             (double)N * C * H * W * (dtype == WSOVOD_BF16 ? 2 : 4));
+#define LAUNCH_LOOP(T, CPL, AM)                                                                                      \
   do {                                                                                                               \
-    auto k = roi_loop_pool_fwd_nhwc_rows<T, CPL>;                                                                    \
+    auto k = roi_loop_pool_fwd_nhwc_rows<T, CPL, AM>;                                                                \
     if (lds > 64 * 1024) WS_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds), \
                                       "wsovod_roi_loop_pool_forward: LDS opt-in");                                   \
-    hipLaunchKernelGGL(k, dim3(R * cgroups), dim3(64 * nwaves), lds, s, (const T*)feat, rois, R, C, H, W, ph, pw,      \
-                       spatial_scale, context_ratio, out, argmax, cgroups, share);                                   \
+    hipLaunchKernelGGL(k, dim3(R * cgroups), dim3(64 * nwaves), lds, s, (const T*)feat, rois, roi_scale, R, C, H, W, ph, \
+                       pw, spatial_scale, context_ratio, out, out_dtype, out_hi, argmax, cgroups, share);             \
+  } while (0)
+#define LAUNCH_LOOP_AM(T, CPL)                                                     \
+  do {                                                                             \
+    if (argmax) LAUNCH_LOOP(T, CPL, true); else LAUNCH_LOOP(T, CPL, false);        \
   } while (0)
   if (dtype == WSOVOD_BF16) {
-    if (two) LAUNCH_LOOP(bf16_t, 2); else LAUNCH_LOOP(bf16_t, 1);
+    if (two) LAUNCH_LOOP_AM(bf16_t, 2); else LAUNCH_LOOP_AM(bf16_t, 1);
   } else {
-    if (two) LAUNCH_LOOP(float, 2); else LAUNCH_LOOP(float, 1);
+    if (two) LAUNCH_LOOP_AM(float, 2); else LAUNCH_LOOP_AM(float, 1);
   }
+#undef LAUNCH_LOOP_AM
 #undef LAUNCH_LOOP
   WS_CHECK_LAUNCH("wsovod_roi_loop_pool_forward");
   return WSOVOD_OK;
+}
+
+int wsovod_roi_loop_pool_forward(const void* feat, int dtype, int layout, const float* rois, int R, int N, int C, int H,
+                                 int W, int ph, int pw, float spatial_scale, float context_ratio, float* out,
+                                 int* argmax, wsovod_stream_t stream) {
+  return roi_loop_pool_forward_impl(false, feat, dtype, layout, rois, nullptr, R, N, C, H, W, ph, pw, spatial_scale,
+                                    context_ratio, out, WSOVOD_F32, argmax, nullptr, stream);
+}
+
+int wsovod_roi_loop_pool_forward_ex(const void* feat, int dtype, int layout, const float* rois, const float* roi_scale, int R,
+                                    int N, int C, int H, int W, int ph, int pw, float spatial_scale, float context_ratio,
+                                    void* out, int out_dtype, int* argmax, void* out_hi, wsovod_stream_t stream) {
+  return roi_loop_pool_forward_impl(true, feat, dtype, layout, rois, roi_scale, R, N, C, H, W, ph, pw, spatial_scale,
+                                    context_ratio, out, out_dtype, argmax, out_hi, stream);
 }
 
 int wsovod_roi_pool_backward(const float* grad_out, const float* rois, const float* roi_scale, const int* argmax, int R,

@@ -524,8 +524,39 @@ class _RoILoopPool(Function):
         return g.to(ctx.in_dtype), None, None, None
 
 
-def roi_loop_pool(feat, rois, output_size, spatial_scale):
-    return _RoILoopPool.apply(feat, rois, tuple(output_size), float(spatial_scale))
+class _RoILoopPoolFused(Function):
+    """The 3-output pool with the fused objectness scale and output encoding (hip_ops.roi_loop_pool_forward_fused), the
+    form the ROI heads call: the argmax is tracked only when the map takes a gradient; the backward scatters
+    grad * roi_scale[r] through it, the rois and the scale repeated for the three parts (ROILoopPool_cuda.cu:207-243)."""
+
+    @staticmethod
+    def forward(ctx, feat, rois, output_size, spatial_scale, roi_scale, out_dtype):
+        need_grad = feat.requires_grad
+        out, argmax = H.roi_loop_pool_forward_fused(feat, rois, spatial_scale, output_size, roi_scale=roi_scale,
+                                                    out_dtype=out_dtype, need_argmax=need_grad,
+                                                    want_hi=out_dtype in (H.X2, H.MX) and _WANT_HI.on)
+        ctx.shape = tuple(feat.shape)
+        ctx.cl = not feat.is_contiguous()
+        ctx.in_dtype = feat.dtype
+        if need_grad:
+            ctx.save_for_backward(rois, argmax, roi_scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        rois, argmax, roi_scale = ctx.saved_tensors
+        g = H.roi_pool_backward(grad_output, rois.repeat(3, 1), argmax, ctx.shape, channels_last=ctx.cl,
+                                roi_scale=roi_scale.repeat(3) if roi_scale is not None else None)
+        return g.to(ctx.in_dtype), None, None, None, None, None
+
+
+def roi_loop_pool(feat, rois, output_size, spatial_scale, roi_scale=None, out_dtype=None):
+    """Without roi_scale / out_dtype: the reference's op as it is bound (fp32 values and argmax, cast to the map's dtype).
+    With either: the fused form."""
+    if roi_scale is None and out_dtype is None:
+        return _RoILoopPool.apply(feat, rois, tuple(output_size), float(spatial_scale))
+    return _RoILoopPoolFused.apply(feat, rois, tuple(output_size), float(spatial_scale), roi_scale, out_dtype or feat.dtype)
 
 
 def roi_pool(feat, rois, output_size, spatial_scale, roi_scale=None, out_dtype=None):

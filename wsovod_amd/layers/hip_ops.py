@@ -305,6 +305,33 @@ def roi_loop_pool_forward(feat, rois, spatial_scale, output_size, context_ratio=
     return out, arg
 
 
+def roi_loop_pool_forward_fused(feat, rois, spatial_scale, output_size, roi_scale=None, out_dtype=None, need_argmax=True,
+                                want_hi=False, context_ratio=1.8):
+    """The 3-output pool with the objectness scale and the output encoding fused (wsovod_roi_loop_pool_forward_ex) ->
+    (out (3R,C,ph,pw) = [region | frame | context], argmax int32 or None).  Row r of all three parts is multiplied by
+    roi_scale[r] in fp32, then written as `out_dtype` (a torch dtype, X2 or MX; a carrier is tagged as roi_pool_forward tags
+    it).  want_hi (X2 / MX): also the plain bf16 rounding, fetched later with x2_hi_pop(out) -- planar bf16x2 where it fits."""
+    require_gpu(feat, rois, roi_scale)
+    layout, N, Cc, Hh, Ww = feature_layout(feat)
+    if layout != NHWC and feat.is_contiguous(memory_format=torch.channels_last):
+        layout = NHWC  # (a 1 x 1 map or one channel is both NCHW- and NHWC-contiguous)
+    rois = _rois_f32(rois)
+    ph, pw = output_size
+    R = rois.shape[0]
+    out_dtype = out_dtype or feat.dtype
+    out = _out_empty((3 * R, Cc, ph, pw), storage_dtype(out_dtype), feat.device)
+    arg = _out_empty((3 * R, Cc, ph, pw), torch.int32, feat.device) if need_argmax else None
+    if roi_scale is not None:
+        roi_scale = roi_scale.to(torch.float32).contiguous()
+    planar = bool(want_hi and out_dtype == X2 and R > 0 and _x2_planar_ok(3 * R, Cc * ph * pw))
+    hi = torch.empty_like(out, dtype=torch.bfloat16) if (want_hi and out_dtype in (X2, MX) and R > 0 and not planar) else None
+    check(lib().wsovod_roi_loop_pool_forward_ex(
+        ptr(feat), dtype_code(feat.dtype), layout, ptr(rois), ptr(roi_scale), R, N, Cc, Hh, Ww, ph, pw,
+        C.c_float(spatial_scale), C.c_float(context_ratio), ptr(out), BF16X2P if planar else fmt_code(out_dtype), ptr(arg),
+        ptr(hi), stream()), "roi_loop_pool_forward_fused")
+    return _tag_pooled(out, out_dtype, planar, hi), arg
+
+
 def roi_pool_backward(grad_out, rois, argmax, input_shape, channels_last=False, roi_scale=None):
     require_gpu(grad_out, rois, argmax)
     N, Cc, H, W = input_shape

@@ -32,7 +32,9 @@ class RoIPool(nn.Module):
 
 
 class ROILoopPool(nn.Module):
-    """wsovod.layers.ROILoopPool(output_size, spatial_scale): (3R, C, ph, pw) = [region | frame | context]."""
+    """wsovod.layers.ROILoopPool(output_size, spatial_scale): (3R, C, ph, pw) = [region | frame | context].  With a
+    `roi_scale` or an `out_dtype` (this implementation's extensions, as on the other poolers): the fused kernel -- row r of
+    all three parts times roi_scale[r], written in fc1's operand format."""
 
     def __init__(self, output_size, spatial_scale):
         super().__init__()
@@ -41,9 +43,12 @@ class ROILoopPool(nn.Module):
 
     def forward(self, input, rois, roi_scale=None, out_dtype=None):
         assert rois.dim() == 2 and rois.size(1) == 5
-        assert roi_scale is None, "the objectness scale is applied by the caller for ROILoopPool"
-        out = Fn.roi_loop_pool(input, rois, self.output_size, self.spatial_scale)
-        return out if out_dtype is None else out.to(out_dtype)
+        if roi_scale is None and out_dtype is None:  # the reference's op as it is bound
+            return Fn.roi_loop_pool(input, rois, self.output_size, self.spatial_scale)
+        # the fused form: objectness scale and output encoding inside the kernel, which reads channels-last maps only
+        if not input.is_contiguous(memory_format=torch.channels_last):
+            input = input.contiguous(memory_format=torch.channels_last)
+        return Fn.roi_loop_pool(input, rois, self.output_size, self.spatial_scale, roi_scale, out_dtype)
 
 
 class ROIAlign(nn.Module):

@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from ..config import ROI_HEADS_REGISTRY, configurable
+from ..layers import carrier
 from ..layers import functions as Fn
 from ..layers import hip_ops as H
 from ..layers import mx_guard
@@ -168,8 +169,9 @@ class WSOVODROIHeads(ROIHeads):
     def _pool_dtype_for(self, rows):
         """"parity_mx": the box head's FC layers take the f16mx kernel (one 256 x 256 tile shape) from 4096 pooled rows up --
         16 row tiles x 16 column tiles = one workgroup per CU; below, the bf16x2 path's split-K forms win (same mode, same
-        bound)."""
-        if H.mx_active() and self.pooler_type in ("ROIPool", "ROIAlignV2", "ROIAlign") and rows >= self.MX_MIN_ROWS:
+        bound).  `rows` is what fc1 contracts: R for the one-output poolers, 3R for ROILoopPool."""
+        if H.mx_active() and self.pooler_type in ("ROIPool", "ROIAlignV2", "ROIAlign", "ROILoopPool") \
+                and rows >= self.MX_MIN_ROWS:
             return H.MX
         return self.pool_dtype
 
@@ -273,15 +275,13 @@ class WSOVODROIHeads(ROIHeads):
         boxes = self.boxes_cat(proposals)
         rois, roi_scale = H.format_rois(boxes, segment_offsets([len(p) for p in proposals], boxes.device),
                                         H.cat_rows([x.objectness_logits for x in proposals]))
-        if self.pooler_type == "ROILoopPool" and H.x3_active() == "x2":
-            raise NotImplementedError('MODEL.HIP.PRECISION "parity" does not cover POOLER_TYPE ROILoopPool (use "bf16x3f")')
-        if self.pooler_type == "ROILoopPool":  # (3R, C, 7, 7) = [region | frame | context], roi_heads.py:727-739
-            out = self.box_pooler(feats, [x.proposal_boxes for x in proposals], out_dtype=torch.float32, rois=rois)
-            return (out * roi_scale.repeat(3).view(-1, 1, 1, 1)).to(self.compute_dtype)
+        # ROILoopPool: (3R, C, 7, 7) = [region | frame | context] (roi_heads.py:727-739); the scale of box r is applied to
+        # its three rows inside the kernel, and fc1 sees 3R rows: that count picks the carrier
+        rows = int(rois.shape[0]) * (3 if self.pooler_type == "ROILoopPool" else 1)
         Fn._WANT_HI.on = self.training and os.environ.get("WSOVOD_X2_HI", "1") != "0"  # (bf16x2 pooling only) a plain bf16 copy for fc1's dW
         try:
             pooled = self.box_pooler(feats, [x.proposal_boxes for x in proposals], roi_scale=roi_scale,
-                                     out_dtype=self._pool_dtype_for(int(rois.shape[0])), rois=rois)
+                                     out_dtype=self._pool_dtype_for(rows), rois=rois)
             if H.mx_of(pooled):
                 mx_guard.audit("roi_heads.pooled", pooled)
             return pooled
@@ -304,9 +304,23 @@ class WSOVODROIHeads(ROIHeads):
         box_features = self.box_head(box_features)
         if self.pooler_type == "ROILoopPool":  # contextlocnet: the neck ran on region, frame and context rows
             parts = list(torch.chunk(box_features, 3, dim=0))
+            if H.x3_active() == "x2":
+                # "parity" / "parity_mx": the neck's output is a bf16x2 carrier whose 32-value groups run along a row, so a
+                # block of rows is a carrier of the same format -- said so, torch drops the tag on a slice
+                parts = [carrier.like(box_features, q) for q in parts]
             if data_aware_features is not None:
                 nums = [len(p) for p in proposals]
                 daf = data_aware_features.to(torch.float32)
+                if H.x3_active() == "x2":
+                    # torch arithmetic cannot read a carrier: the group-row add of the one-output path, once per part
+                    dev = box_features.device
+                    if daf.size(0) == len(proposals) and daf.size(0) != sum(nums):
+                        seg = segment_offsets(nums, dev)
+                        row_group = H.const_tensor([i for i, n in enumerate(nums) for _ in range(n)], torch.int32, dev)
+                    else:
+                        seg = torch.arange(sum(nums) + 1, dtype=torch.int32, device=dev)
+                        row_group = torch.arange(sum(nums), dtype=torch.int32, device=dev)
+                    return [Fn.add_group_rows(q, daf, row_group, seg) for q in parts]
                 if daf.size(0) == len(proposals) and daf.size(0) != sum(nums):
                     daf = torch.cat([daf[i:i + 1].expand(n, -1) for i, n in enumerate(nums)])
                 parts = [(q.float() + daf).to(q.dtype) for q in parts]

@@ -238,10 +238,10 @@ def add_wsovod_config(cfg):
     _C.SOLVER.BACKBONE_MULTIPLIER = 1.0
     # hot-path extensions of this implementation (not in the reference)
     _C.MODEL.HIP = C()
-    # "bf16" (bf16 MFMA, fp32 accumulate) | "fp32" (exact-fp32 MFMA) | "bf16x3" (fp32 tensors, bf16 MFMA on hi/lo-split
-    # operands: fp32-grade products at a third of the bf16 rate) | "bf16x3f" (the split in the forward pass only, plain
-    # bf16 backward: fp32-grade logits, bf16-grade gradients) | "parity" (the fast tolerance-meeting mode: the forward
-    # split of "bf16x3f" on the activation format / kernels built for it -- DESIGN.md section 3)
+    # "bf16" (bf16 MFMA, fp32 accumulate) | "fp32" (exact-fp32 MFMA) | "bf16x3" (fp32 tensors, bf16 MFMA on hi/lo-split operands)
+    # | "bf16x3f" (that split in the forward pass only, plain bf16 backward) | "parity" (the forward split on the bf16x2 activation
+    # format built for it) | "parity_train" (+ split input gradients) | "parity_mx" (parity with the big
+    # contractions on the f16mx kernels) | "parity_mx_train" (both): what each name sets is ONE table, layers/precision.py:TABLE
     _C.MODEL.HIP.PRECISION = "bf16"
     # range guard of the unscaled f16mx operands ("parity_mx" / "parity_mx_train" only; layers/mx_guard.py):
     # "off" | "warn" | "raise" | "fallback" (to the bf16x2 kernels of "parity"); in training every PERIOD-th step is audited

@@ -14,6 +14,7 @@ from torch.autograd.function import once_differentiable
 from . import carrier
 from . import hip_ops as H
 from . import operand_cache
+from .precision import _bwd_split, _no_split, _pt_dx, backward_split, x2_active  # noqa: F401 -- (backward_split: re-exported)
 
 
 _USE_TN = os.environ.get("WSOVOD_DISABLE_TN", "0") != "1"  # A/B switch for the transposed-read dW kernel
@@ -46,58 +47,6 @@ def weight_shadow(weight, cd):
     return operand_cache.lookup(weight, "bf16", lambda src: H.cast(src, cd), variant=cd, store=weight.is_leaf)
 
 
-def _x2_mode():
-    """MODEL.HIP.PRECISION = "parity": the activations that reach the Linear fronts are bf16x2 tensors (hip_ops.X2)."""
-    return H.x3_active() == "x2"
-
-
-class _BwdSplitState(threading.local):
-    on = False
-
-
-_BWD_SPLIT = _BwdSplitState()
-
-
-@contextlib.contextmanager
-def backward_split(on=True):
-    """MODEL.HIP.PRECISION = "parity_train": Functions created inside keep the hi/lo split in their BACKWARD contractions
-    too (three bf16 MFMA products on fp32 gradients, decoded bf16x2 activations and fp32 master weights -- the arithmetic
-    of the "bf16x3" mode's backward) instead of plain bf16 products on the hi halves.  The "parity" forward is unchanged;
-    what changes is the trained trajectory (tests/test_gpu_full_size.py: five optimizer steps against the oracle).
-    Which contractions keep it (WSOVOD_PT_SPLIT, default "dx"): the ablation of round 6 (tools/parity_train_ablation.py,
-    profiles/r06_parity_train_ablation.json) shows that the trajectory error of the plain-bf16 backward comes from the
-    INPUT-gradient contractions dX = dA W -- their rounding is inherited by every layer further back -- and not from the
-    weight gradients dW = dA^T X, whose rounding is independent noise per element: after five optimizer steps the logits are
-    6.7e-3 from the oracle's with neither, 7.1e-3 with the split in dW only, 4.0e-4 with the split in dX only, 4.2e-4 with
-    both.  "dw,dx" keeps both (the "bf16x3" mode's backward, ~+35 % step time instead of ~+11 %)."""
-    prev = _BWD_SPLIT.on
-    _BWD_SPLIT.on = bool(on)
-    try:
-        yield
-    finally:
-        _BWD_SPLIT.on = prev
-
-
-def _bwd_split():
-    """-> frozenset of {"dw", "dx"}: which backward contractions of a Function created now keep the split."""
-    if not _BWD_SPLIT.on:
-        return frozenset()
-    which = os.environ.get("WSOVOD_PT_SPLIT", "dx")
-    return frozenset(w for w in which.split(",") if w in ("dw", "dx"))
-
-
-def _pt_dx():
-    """WSOVOD_PT_DX: how a split input gradient dX = dA W is contracted under "parity_mx_train" -- "x2" (default): ONE bf16x2
-    contraction on a masked gradient written as bf16x2 in one pass and the cached bf16x2 encoding of W^T; "x3": the
-    generic route of "parity_train" (fp32 dA, a split pass, the fp32 master transposed and split at every step)."""
-    return "x3" if os.environ.get("WSOVOD_PT_DX", "x2") == "x3" else "x2"
-
-
-def _no_split(x3):
-    """The x3 state a backward pass runs under: the forward-only modes ("fwd", "x2") contract in plain bf16."""
-    return x3 if x3 not in ("fwd", "x2") else False
-
-
 class _Linear(Function):
     """y = dropout(relu(x @ W^T + b)); x (M,K) in the compute dtype, W fp32 master (N,K).
     "parity" precision: x is bf16x2, the products are three-MFMA sums on the bf16x2 weight, y is bf16x2 (out_dtype =
@@ -106,7 +55,7 @@ class _Linear(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu, dropout_p, seed, out_dtype, seed_add=None, grad_on=True):
-        ctx.x2 = _x2_mode()
+        ctx.x2 = x2_active()
         ctx.y_x2 = out_dtype == H.X2
         x_hi = y_mask = None
         if ctx.x2 and H.mx_of(x):
@@ -185,7 +134,7 @@ class _Linear(Function):
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
         s_dw, s_dx = need_dw and "dw" in ctx.bwd, need_dx and "dx" in ctx.bwd
-        dx_x2 = s_dx and ctx.mx_mode and _pt_dx() == "x2"  # "parity_mx_train": dX as ONE bf16x2 contraction (_dx_x2)
+        dx_x2 = s_dx and ctx.mx_mode and _pt_dx() != "x3"  # "parity_mx_train": dX as ONE bf16x2 contraction (_dx_x2)
         dy = _contig2d(dy)
         scale = 1.0 / (1.0 - ctx.dropout_p) if ctx.dropout_p > 0 else 1.0
         Mp, Np = _pad(M, 64), _pad(N, 8)
@@ -333,7 +282,7 @@ class _LinearGroup(Function):
         first = [0]
         for h in heads:
             first.append(first[-1] + h[2])
-        ctx.x2 = _x2_mode()
+        ctx.x2 = x2_active()
         # (under "parity_mx" / "parity_mx_train" the LAST FC layer of the box head hands bf16x2 to the heads at every row
         # count -- box_head.py -- so no f16mx carrier reaches the group, and its backward split stays the bf16x2 one)
         carrier.refuse("linear_group", (x,), reads=(carrier.X2P,))  # (a planar carrier: gemm_nt's own refusal, as before)
@@ -593,14 +542,14 @@ class _CosineLogits(Function):
     @staticmethod
     def forward(ctx, z, wn, wnT, temperature, normalize, bias_vec):
         rs = H.row_l2norm_scale(z, temperature) if normalize else None
-        if _x2_mode():  # z is a real fp32 tensor here (the norm reads it): encode it and the class matrix, 3-MFMA products
+        if x2_active():  # z is a real fp32 tensor here (the norm reads it): encode it and the class matrix, 3-MFMA products
             logits = H.gemm_nt(H.x2_encode(z), H.x2_cached(wn), x2=True, row_scale=rs, bias=bias_vec, out_dtype=torch.float32)
         else:
             logits = H.gemm_nt(z, wn, row_scale=rs, bias=bias_vec, out_dtype=torch.float32)
         ctx.save_for_backward(z, wnT)
         ctx.cfg = (temperature, normalize, bias_vec is not None)
         ctx.x3 = H.x3_active()
-        ctx.bwd = _bwd_split() if ctx.x3 == "x2" else frozenset()
+        ctx.bwd = _bwd_split() if x2_active() else frozenset()
         return logits
 
     @staticmethod
@@ -767,7 +716,7 @@ class _AddGroupRows(Function):
     @staticmethod
     def forward(ctx, x, add, row_group, seg_offsets):
         ctx.save_for_backward(seg_offsets)
-        return H.add_group_rows(x, row_group, add, x2=_x2_mode())  # "parity": x and the result are bf16x2
+        return H.add_group_rows(x, row_group, add, x2=x2_active())  # "parity": x and the result are bf16x2
 
     @staticmethod
     @once_differentiable

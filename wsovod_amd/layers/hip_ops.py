@@ -13,6 +13,7 @@ import torch
 from .. import _lib
 from .._lib import BF16, BF16X2, BF16X2P, F16MX, F32, NCHW, NHWC, GemmDesc, check, dtype_code, lib, ptr, require_gpu, stream
 from . import carrier, operand_cache
+from .precision import mx_active, mx_mode, x2_active, x3_active, x3_mode  # noqa: F401 -- the modes' state and scopes, re-exported
 
 
 _CONST_CACHE = {}
@@ -648,72 +649,6 @@ def stem_conv1_x2(images_u8, sizes, mean, std, w32_x2, bias):
 # bf16x3 mode (MODEL.HIP.PRECISION = "bf16x3"): fp32 tensors everywhere, every contraction evaluated on the bf16 MFMA
 # kernels as sum ah*bh + ah*bl + al*bh over operands split by wsovod_split3_bf16 (include/wsovod_hip.h).
 # ---------------------------------------------------------------------------------------
-import threading
-
-
-class _X3StateT(threading.local):
-    """Per-thread: a TTA / data-loader thread must neither see nor clobber the mode of the autograd thread."""
-    active = False
-
-
-_X3State = _X3StateT()
-
-
-class x3_mode:
-    """Context manager: fp32 x fp32 contractions issued inside go through the bf16x3 split.  Model entry points enter
-    it when their precision is "bf16x3" (mode "full"), "parity" (mode "x2": bf16x2 activations, see above; fp32 x fp32
-    contractions issued without the x2 tag -- the RPN head on the fp32 res5 map -- still take the split below) or "bf16x3f"
-    (mode "fwd": the split only in the forward pass;
-    the backward contractions then run as plain bf16 on casts of the saved fp32 tensors -- forward logits of fp32
-    grade, gradients of the bf16 mode's grade).  Autograd Functions capture `x3_active()` in forward and act on it in
-    backward (the autograd engine runs backward outside the forward's context)."""
-
-    def __init__(self, on=True):
-        self.on = ("full" if on is True else on) if on else False
-
-    def __enter__(self):
-        self.prev = _X3State.active
-        _X3State.active = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _X3State.active = self.prev
-        return False
-
-
-class _MxStateT(threading.local):
-    on = False
-
-
-_MxState = _MxStateT()
-
-
-class mx_mode:
-    """Context manager (MODEL.HIP.PRECISION = "parity_mx"): inside the "x2" (parity) mode, the big forward contractions -- the
-    res4 / res5 convs and the box head's FC layers -- take the block-scaled f16mx kernels (wsovod_gemm_f16mx) and the tensors
-    between them travel as unit-scale f16mx carriers instead of bf16x2."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.prev = _MxState.on
-        _MxState.on = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _MxState.on = self.prev
-        return False
-
-
-def mx_active():
-    return bool(_MxState.on) and x3_active() == "x2"
-
-
-def x3_active():
-    return _X3State.active
-
-
 def split3_bf16(src, side, stack_rows=False, rows_pad=None, out=None):
     """(rows, cols) fp32 (row stride >= cols) -> bf16 blocks [hi | hi | lo] (side 0, A operand) or [hi | lo | hi]
     (side 1, B operand): side by side along the columns -> (rows, 3 cols), or with stack_rows stacked along the rows
@@ -782,7 +717,7 @@ def gemm_nt(A, B, *, out=None, out_dtype=None, out_t=None, alpha=1.0, row_scale=
     carrier.refuse("gemm_nt", (residual,), reads=(carrier.X2P,))
     if x2 and (A.dtype != torch.float32 or B.dtype != torch.float32):
         raise RuntimeError("wsovod_hip gemm: bf16x2 operands travel as float32-typed tensors")
-    if not x2 and _X3State.active and A.dtype == torch.float32 and B.dtype == torch.float32:
+    if not x2 and x3_active() and A.dtype == torch.float32 and B.dtype == torch.float32:
         if M is not None or N is not None or K is not None or A2 is not None:
             raise RuntimeError("bf16x3: explicit M/N/K overrides / a fused shortcut input are not supported")
         return _gemm_nt_x3(A, B, conv=conv, out=out, out_dtype=out_dtype or torch.float32, out_t=out_t, alpha=alpha,

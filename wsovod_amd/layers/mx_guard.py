@@ -25,8 +25,10 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from .precision import TABLE
+
 MODES = ("off", "warn", "raise", "fallback")
-MX_PRECISIONS = ("parity_mx", "parity_mx_train")
+MX_PRECISIONS = tuple(n for n, p in TABLE.items() if p.mx)  # the names with f16mx operands
 MAX_SITES = 256
 
 SiteReport = namedtuple("SiteReport", "audited nonfinite top_code max_abs")

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import BACKBONE_REGISTRY
-from ..layers import carrier, hip_ops as H, mx_guard
+from ..layers import carrier, hip_ops as H, mx_guard, precision as P
 from ..structures import ShapeSpec
 
 __all__ = ["BasicStem", "BasicBlock", "BottleneckBlock", "ResNet", "FrozenForwardMixin", "FrozenBatchNorm2d", "Conv2d",
@@ -96,11 +96,6 @@ class Conv2d(nn.Module):
         return self._folded[1], self._folded[2]
 
 
-def _x2():
-    """MODEL.HIP.PRECISION = "parity": feature maps between the convs are bf16x2 NHWC tensors (hip_ops.X2)."""
-    return H.x3_active() == "x2"
-
-
 def _folded_x2(conv, cin_pad=None):
     """bf16x2 encoding of the folded fp32 weight rows ([Cout][kh*kw*Cin], Cin a multiple of 32: a tap's channels are
     whole 32-value groups, so encoding the flat rows encodes every tap), cached with the fold."""
@@ -149,7 +144,7 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
                                   out_fp32=out_fp32))
         return carrier.like(parts[0], torch.cat(parts))
     geom = dict(n_img=N, H=Hh, W=Ww, Cin=Cin, Ho=Ho, Wo=Wo, KH=k, KW=k, stride=s, pad=p, dil=d)
-    if _x2() and H.mx_of(x):
+    if H.x2_active() and H.mx_of(x):
         # "parity_mx": x (and residual / shortcut input) are unit-scale f16mx maps; fp16 hi*hi + block-scaled e4m3 cross terms
         # on the f16mx weights (per-row scales, encoded once: the stages are frozen or re-encoded per optimizer step); the
         # output is f16mx again, or real fp32 for the map that leaves the backbone
@@ -171,7 +166,7 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
         if fmt == H.MX:
             mx_guard.audit(conv, out)
         return out.view(N, Ho, Wo, conv.out_channels)  # (a whole view of what gemm_mx tagged)
-    if _x2():
+    if H.x2_active():
         # x (and residual / shortcut input) are bf16x2 maps; three-MFMA products on the bf16x2 weights; the output is
         # bf16x2 again, or real fp32 for the map that leaves the backbone (out_fp32)
         fmt = torch.float32 if out_fp32 else H.X2
@@ -213,7 +208,7 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
 def _fusable_shortcut(sc, x):
     """The block's projection shortcut can ride in its last conv's accumulation: 1x1, stride 1, a whole number of
     K-steps of channels, bf16 / exact-fp32 operands (the bf16x3 modes split their operands and keep the separate launch)."""
-    if sc is None or (H.x3_active() and not _x2()) or os.environ.get("WSOVOD_FUSE_SHORTCUT", "1") == "0":
+    if sc is None or (H.x3_active() and not H.x2_active()) or os.environ.get("WSOVOD_FUSE_SHORTCUT", "1") == "0":
         return False
     kstep = 64 if x.dtype == torch.bfloat16 else 32  # (bf16x2: 32 values = 64 bf16 slots)
     return sc.kernel_size == 1 and sc.stride == 1 and sc.padding == 0 and sc.in_channels % kstep == 0 and x.is_contiguous()
@@ -238,7 +233,7 @@ class _PoolMixin:
         if not self.has_pool:
             return out
         # stride 1: ZeroPad2d((0,1,0,1)) + MaxPool2d(2, 1); else MaxPool2d(2, stride)  (resnet_wsl.py:85-92)
-        return H.maxpool2x2_nhwc(out, self.pool_stride, zero_pad_br=self.pool_stride == 1, x2=_x2())
+        return H.maxpool2x2_nhwc(out, self.pool_stride, zero_pad_br=self.pool_stride == 1, x2=H.x2_active())
 
 
 class BasicBlock(CNNBlockBase, _PoolMixin):
@@ -343,7 +338,7 @@ class BasicStem(CNNBlockBase):
         return wpad[1], b
 
     def forward_uint8(self, images_u8, sizes, pixel_mean, pixel_std):
-        if _x2():  # "parity": the fused kernel on the bf16x2 encoding of the (64, 32) fp32 weight, bf16x2 output
+        if H.x2_active():  # "parity": the fused kernel on the bf16x2 encoding of the (64, 32) fp32 weight, bf16x2 output
             w32, b = self._im2col_weight(torch.float32)
             return self._tail(H.stem_conv1_x2(images_u8, sizes, pixel_mean, pixel_std, H.x2_cached(w32), b))
         w32, b = self._im2col_weight(torch.bfloat16)
@@ -388,11 +383,8 @@ def _torch_block(block, x):
 
 
 def forward_precision(name):
-    """MODEL.HIP.PRECISION "parity_train" = the "parity" forward (bf16x2 activations, three products) + a backward that
-    keeps the split too (layers/functions.py:backward_split): every module sees "parity", the meta-arch sets the flag.
-    "parity_mx" likewise: the parity forward with its big contractions on the f16mx kernels (hip_ops.mx_mode), and
-    "parity_mx_train" = that forward + the backward split (both flags)."""
-    return "parity" if name in ("parity_train", "parity_mx", "parity_mx_train") else name
+    """The precision every module sees (layers/precision.py:TABLE); the meta-arch enters a composite name's flags."""
+    return P.of(name).forward
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -568,7 +560,7 @@ class _TrainableStage(torch.autograd.Function):
         if _hip_backward_ok(ctx.stage, ctx.x3):
             return _TrainableStage._backward_hip(ctx, dy, x, params)
         with torch.no_grad():  # the saved map in its on-device format (bf16x2 carrier / bf16 / fp32 NHWC) -> fp32 NCHW
-            x32 = H.x2_decode(x.reshape(-1, x.shape[-1])).view(x.shape) if ctx.x3 == "x2" else x.float()
+            x32 = H.x2_decode(x.reshape(-1, x.shape[-1])).view(x.shape) if P.is_x2(ctx.x3) else x.float()
             x32 = x32.permute(0, 3, 1, 2).contiguous()
         need_dx = ctx.needs_input_grad[2]
         x32.requires_grad_(need_dx)
@@ -578,7 +570,7 @@ class _TrainableStage(torch.autograd.Function):
                 y = _torch_block(block, y)
         wanted = ([x32] if need_dx else []) + [p for p in params if p.requires_grad]
         grads = list(torch.autograd.grad(y, wanted, dy.float().permute(0, 3, 1, 2), allow_unused=True))
-        dx = grads.pop(0).permute(0, 2, 3, 1).contiguous().to(x.dtype if ctx.x3 != "x2" else torch.float32) if need_dx else None
+        dx = grads.pop(0).permute(0, 2, 3, 1).contiguous().to(torch.float32 if P.is_x2(ctx.x3) else x.dtype) if need_dx else None
         it = iter(grads)
         return (None, None, dx, *[next(it) if p.requires_grad else None for p in params])
 
@@ -605,7 +597,7 @@ class _TrainableStem(torch.autograd.Function):
         cd = torch.float32 if (ctx.x3 is False and net.compute_dtype == torch.float32) else torch.bfloat16
         with torch.no_grad():
             with H.x3_mode(ctx.x3):
-                x2 = _x2()
+                x2 = H.x2_active()
                 a1 = net._stem_conv1(images_u8, sizes, mean, std)  # (bf16x2 maps are tagged by the kernel fronts)
                 a2 = hip_conv(a1, stem.conv2, relu=True)
                 a3 = hip_conv(a2, stem.conv3, relu=True)  # (the forward pools in this conv's epilogue: same bits)
@@ -642,7 +634,7 @@ def _stage_backward_hip(ctx, dy, x, params):
             # x came through ctx.saved_tensors, which does not promise to hand back the tagged object: its format is stated
             # again from the mode.  Every other map of the stage is a fresh kernel output, tagged by its front; the real-fp32
             # map that leaves the backbone is untagged by construction
-            acts, cur = [], (carrier.tag(x, H.X2) if _x2() else x)
+            acts, cur = [], (carrier.tag(x, H.X2) if H.x2_active() else x)
             for b in blocks:
                 nxt, ins, out = _block_forward_saving(b, cur)
                 acts.append((ins, out))
@@ -672,7 +664,40 @@ class FrozenForwardMixin:
 
     @property
     def compute_dtype(self):
-        return torch.bfloat16 if self.precision == "bf16" else torch.float32  # "fp32" and "bf16x3" carry fp32 tensors
+        return P.of(self.precision).compute_dtype
+
+    def _emit_fp32_from(self, block):
+        """"parity": bf16x2 maps inside, real fp32 from `block` -- the last one -- for the one map that leaves the backbone."""
+        if P.is_x2(P.of(self.precision).x3):
+            if list(self._out_features) != [self.stage_names[-1]]:
+                raise NotImplementedError('MODEL.HIP.PRECISION "parity" returns the last stage only (bf16x2 maps inside)')
+            block._emits_fp32 = True
+
+    def _float_entry(self, x):
+        """(N,C,H,W) normalised float images -> (NHWC in the compute dtype, Cin 3 padded to one K-step; the entry's mode)."""
+        cd, x3 = self.compute_dtype, P.of(self.precision).x3_float_entry
+        kstep = 64 if (cd == torch.bfloat16 or x3) else 32
+        with torch.no_grad():
+            xn = x.permute(0, 2, 3, 1).to(cd)
+            xn = F.pad(xn, (0, kstep - xn.size(-1))).contiguous()
+        return xn, H.x3_mode(x3)
+
+    MX_MIN_TILES = int(os.environ.get("WSOVOD_MX_MIN_TILES", "200"))  # "parity_mx": fewest tiles of the f16mx kernel's ONE shape
+
+    def _mx_first_stage(self):
+        return self._mx_from() if (H.mx_active() and list(self._out_features) == [self.stage_names[-1]]) else len(self.stages)
+
+    def _mx_min_tiles(self, x, first):
+        """256-row tiles of the smallest conv of the f16mx run that starts with the map x."""
+        return -(-(x.shape[0] * x.shape[1] * x.shape[2]) // 256)
+
+    def _cross_to_mx(self, x, si, mx_from):
+        """Ahead of stage `si`: the map that crosses from the bf16x2 layers to the f16mx ones (enough tiles: see above)."""
+        if si == mx_from and si > 0 and self._mx_min_tiles(x, si) >= self.MX_MIN_TILES:
+            with torch.no_grad():
+                x = H.mx_from_x2(x)
+                mx_guard.audit("backbone.mx_from_x2", x)
+        return x
 
     def _param_list(self):
         cached = getattr(self, "_params_cache", None)
@@ -692,7 +717,7 @@ class FrozenForwardMixin:
         allow_graph: the caller consumes the maps before its next call with this shape (the training step's frozen
         forward): small batches may then come from a captured HIP graph, whose outputs are that graph's STATIC buffers
         -- overwritten by the next replay.  inference() / TTA keep the eager launches (fresh tensors)."""
-        with H.x3_mode({"bf16x3": "full", "bf16x3f": "fwd", "parity": "x2"}.get(self.precision, False)):
+        with H.x3_mode(P.of(self.precision).x3):
             if allow_graph and self.graph_max_batch and images_u8.is_cuda and images_u8.size(0) <= self.graph_max_batch \
                     and not self.has_trainable_stage:
                 g = self._graph_for(images_u8, sizes, pixel_mean, pixel_std)
@@ -746,6 +771,8 @@ class FrozenForwardMixin:
             cache[key] = g
         return g or None
 
+    size_divisibility = 0
+
     def output_shape(self):
         return {name: ShapeSpec(channels=self._out_feature_channels[name], stride=self._out_feature_strides[name])
                 for name in self._out_features}
@@ -783,18 +810,11 @@ class ResNet(FrozenForwardMixin, nn.Module):
             out_features = [name]
         self._out_features = out_features
         assert len(self._out_features)
-        if precision == "parity":  # bf16x2 maps inside, real fp32 for the one map that leaves the backbone
-            if list(out_features) != [self.stage_names[-1]]:
-                raise NotImplementedError('MODEL.HIP.PRECISION "parity" returns the last stage only (bf16x2 maps inside)')
-            list(self.stages[-1].children())[-1]._emits_fp32 = True
+        self._emit_fp32_from(list(self.stages[-1].children())[-1])
         children = [x[0] for x in self.named_children()]
         for out_feature in self._out_features:
             assert out_feature in children, "Available children: {}".format(", ".join(children))
         self.freeze(freeze_at)
-
-    @property
-    def size_divisibility(self):
-        return 0
 
     def _check_frozen(self):
         """The generic float entry (`forward(x)`, a normalised float image) has no trainable-stem path: the stem's first conv
@@ -809,8 +829,6 @@ class ResNet(FrozenForwardMixin, nn.Module):
         """True when a residual stage is trainable (FREEZE_AT < 5): the backbone forward then reads weights the optimizer
         updates, and the trainers may no longer run it ahead of the previous step's update."""
         return any(p.requires_grad for p in self._param_list())
-
-    MX_MIN_TILES = int(os.environ.get("WSOVOD_MX_MIN_TILES", "200"))
 
     def _mx_from(self):
         """"parity_mx": index of the first stage that runs on the f16mx kernels -- the trailing run of FROZEN stages of
@@ -840,14 +858,10 @@ class ResNet(FrozenForwardMixin, nn.Module):
         outputs = {}
         if "stem" in self._out_features:
             outputs["stem"] = x.permute(0, 3, 1, 2)
-        mx_from = self._mx_from() if (H.mx_active() and list(self._out_features) == [self.stage_names[-1]]) else len(self.stages)
+        mx_from = self._mx_first_stage()
         for si, (name, stage) in enumerate(zip(self.stage_names, self.stages)):
             params = self._stage_params(stage)
-            if si == mx_from and si > 0 and -(-(x.shape[0] * x.shape[1] * x.shape[2]) // 256) >= self.MX_MIN_TILES:
-                # the map that crosses from the bf16x2 layers to the f16mx ones (enough 256-row tiles: see _mx_from)
-                with torch.no_grad():
-                    x = H.mx_from_x2(x)
-                    mx_guard.audit("backbone.mx_from_x2", x)
+            x = self._cross_to_mx(x, si, mx_from)
             if torch.is_grad_enabled() and any(p.requires_grad for p in params):
                 _warn_trainable_stage_once(name)
                 x = _TrainableStage.apply(stage, H.x3_active(), x, *params)
@@ -862,13 +876,8 @@ class ResNet(FrozenForwardMixin, nn.Module):
         """x: (N,C,H,W) normalised float image batch -> {name: (N,C',H/8,W/8) channels_last}."""
         assert x.dim() == 4, f"ResNet takes an input of shape (N, C, H, W). Got {x.shape} instead!"
         self._check_frozen()
-        cd = self.compute_dtype
-        x3 = {"bf16x3": "full", "bf16x3f": "fwd", "parity": "fwd"}.get(self.precision, False)  # (float entry: no bf16x2 stem)
-        kstep = 64 if (cd == torch.bfloat16 or x3) else 32
-        with torch.no_grad():
-            xn = x.permute(0, 2, 3, 1).to(cd)
-            xn = F.pad(xn, (0, kstep - xn.size(-1))).contiguous()  # Cin 3 -> one K-step (generic float entry)
-        with H.x3_mode(x3):
+        xn, mode = self._float_entry(x)
+        with mode:
             with torch.no_grad():
                 xs = self.stem(xn)
             return self._run(xs)
@@ -876,8 +885,8 @@ class ResNet(FrozenForwardMixin, nn.Module):
     def _stem_conv1(self, images_u8, sizes, pixel_mean, pixel_std):
         """relu(conv1 (normalised image)) as the stem's forward produces it."""
         stem = self.stem
-        if (self.compute_dtype == torch.bfloat16 or _x2()) and stem.out_channels == 64 and stem.in_channels == 3:
-            if _x2():
+        if (self.compute_dtype == torch.bfloat16 or H.x2_active()) and stem.out_channels == 64 and stem.in_channels == 3:
+            if H.x2_active():
                 w32, b = stem._im2col_weight(torch.float32)
                 return H.stem_conv1_x2(images_u8, sizes, pixel_mean, pixel_std, H.x2_cached(w32), b)
             w32, b = stem._im2col_weight(torch.bfloat16)
@@ -887,7 +896,7 @@ class ResNet(FrozenForwardMixin, nn.Module):
         return H.gemm_nt(a, w32, bias=b, relu=True, out_dtype=a.dtype).view(images_u8.size(0), ho, wo, stem.out_channels)
 
     def _stem_uint8(self, images_u8, sizes, pixel_mean, pixel_std):
-        if (self.compute_dtype == torch.bfloat16 or _x2()) and self.stem.out_channels == 64 and self.stem.in_channels == 3:
+        if (self.compute_dtype == torch.bfloat16 or H.x2_active()) and self.stem.out_channels == 64 and self.stem.in_channels == 3:
             # bf16: one kernel from the uint8 canvas to relu(conv1) (bit-identical to im2col + GEMM, no operand pass)
             return self.stem.forward_uint8(images_u8, sizes, pixel_mean, pixel_std)
         a, ho, wo = H.stem_im2col(images_u8, sizes, pixel_mean, pixel_std, self.compute_dtype)

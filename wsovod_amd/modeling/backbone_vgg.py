@@ -18,15 +18,12 @@ Forward only: every shipped V_16 config freezes the whole backbone (FREEZE_AT: 5
              mx_from_x2 on the run's input, the pools inside the run are the f16mx pool (wsovod_maxpool2x2_nhwc with
              WSOVOD_F16MX: the winner's three fields copied verbatim)
 """
-import os
-
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from ..config import BACKBONE_REGISTRY
 from ..layers import hip_ops as H, mx_guard
-from .backbone import CNNBlockBase, Conv2d, FrozenForwardMixin, _x2, c2_msra_fill, forward_precision, hip_conv
+from .backbone import CNNBlockBase, Conv2d, FrozenForwardMixin, c2_msra_fill, forward_precision, hip_conv
 
 __all__ = ["PlainBlock", "VGG16", "build_vgg_backbone"]
 
@@ -63,7 +60,7 @@ class PlainBlock(CNNBlockBase):
     def _pool(self, x):
         """MaxPool2d(2, stride, padding=0): odd sizes floor; stride 1 gives (H - 1, W - 1)."""
         mx = H.mx_of(x)
-        out = H.maxpool2x2_nhwc(x, self.pool_stride, zero_pad_br=False, x2=_x2() and not mx, mx=mx)
+        out = H.maxpool2x2_nhwc(x, self.pool_stride, zero_pad_br=False, x2=H.x2_active() and not mx, mx=mx)
         if mx:
             mx_guard.audit(self, out)  # (copied fields: in range when the producer's were; audited as every f16mx producer is)
         return out
@@ -85,7 +82,6 @@ class PlainBlock(CNNBlockBase):
 class VGG16(FrozenForwardMixin, nn.Module):
     """vgg.py:124-230."""
 
-    MX_MIN_TILES = int(os.environ.get("WSOVOD_MX_MIN_TILES", "200"))  # (ResNet.MX_MIN_TILES: one tile shape, 256 rows)
     has_trainable_stage = False
 
     def __init__(self, conv5_dilation, freeze_at, num_classes=None, out_features=None, precision="bf16"):
@@ -124,15 +120,8 @@ class VGG16(FrozenForwardMixin, nn.Module):
         assert len(self._out_features)
         for f in self._out_features:
             assert f in self.stage_names, "Available children: {}".format(", ".join(self.stage_names))
-        if precision == "parity":  # bf16x2 maps inside, real fp32 for the one map that leaves the backbone
-            if list(out_features) != [self.stage_names[-1]]:
-                raise NotImplementedError('MODEL.HIP.PRECISION "parity" returns the last stage only (bf16x2 maps inside)')
-            self.stages[-1][0]._emits_fp32 = True
+        self._emit_fp32_from(self.stages[-1][0])
         self.freeze(freeze_at)
-
-    @property
-    def size_divisibility(self):
-        return 0
 
     def freeze(self, freeze_at=0):
         for idx, stage in enumerate(self.stages, start=1):
@@ -170,13 +159,10 @@ class VGG16(FrozenForwardMixin, nn.Module):
     def _run(self, x, first_stage_done=False):
         """x: the NHWC input of plain1 -- or, with first_stage_done, plain1's output."""
         outputs = {}
-        only_last = list(self._out_features) == [self.stage_names[-1]]
-        mx_from = self._mx_from() if (H.mx_active() and _x2() and only_last) else len(self.stages)  # (bf16x2 maps only)
+        mx_from = self._mx_first_stage()
         with torch.no_grad():
             for si, (name, stage) in enumerate(zip(self.stage_names, self.stages)):
-                if si == mx_from and si > 0 and self._mx_min_tiles(x, si) >= self.MX_MIN_TILES:
-                    x = H.mx_from_x2(x)  # the map that crosses from the bf16x2 layers to the f16mx ones
-                    mx_guard.audit("backbone.mx_from_x2", x)
+                x = self._cross_to_mx(x, si, mx_from)
                 if not (si == 0 and first_stage_done):
                     x = stage(x)
                 if name in self._out_features:
@@ -186,19 +172,14 @@ class VGG16(FrozenForwardMixin, nn.Module):
     def forward(self, x):
         """x: (N,C,H,W) normalised float image batch -> {name: (N,C',H',W') channels_last}."""
         assert x.dim() == 4, f"VGG16 takes an input of shape (N, C, H, W). Got {x.shape} instead!"
-        cd = self.compute_dtype
-        x3 = {"bf16x3": "full", "bf16x3f": "fwd", "parity": "fwd"}.get(self.precision, False)  # (float entry: no bf16x2 conv1_1)
-        kstep = 64 if (cd == torch.bfloat16 or x3) else 32
-        with torch.no_grad():
-            xn = x.permute(0, 2, 3, 1).to(cd)
-            xn = F.pad(xn, (0, kstep - xn.size(-1))).contiguous()  # Cin 3 -> one K-step (generic float entry)
-        with H.x3_mode(x3):
+        xn, mode = self._float_entry(x)
+        with mode:
             return self._run(xn)
 
     def _conv1_1(self, images_u8, sizes, pixel_mean, pixel_std):
         """relu(conv1_1(normalised image)): (N, Hp, Wp, 64) NHWC in the precision's activation format."""
         conv = self.stages[0][0].conv1
-        if _x2():
+        if H.x2_active():
             w32, b = _im2col_weight(conv, torch.float32)
             return H.stem_conv1_s1_x2(images_u8, sizes, pixel_mean, pixel_std, H.x2_cached(w32), b)
         if self.compute_dtype == torch.bfloat16:

@@ -101,7 +101,7 @@ class DiscriminativeAdaptationNeck(nn.Sequential):
             # "parity" precision: x arrives as bf16x2 (the pooler wrote it) and every FC hands bf16x2 on; "parity_mx": x arrives
             # as f16mx, the FC layers hand f16mx on among themselves and the last one bf16x2 to the heads
             fmt = None
-            if H.x3_active() == "x2":
+            if H.x2_active():
                 fmt = H.MX if (H.mx_of(x) and k + 1 < len(self.fcs)) else H.X2
             x = Fn.linear(x, fc.weight, fc.bias, relu=True, dropout_p=p, seed=seed, out_dtype=fmt,
                           seed_add=step_term if p > 0 else None)

@@ -17,7 +17,7 @@ from torch import nn
 
 from ..config import BACKBONE_REGISTRY, META_ARCH_REGISTRY, configurable
 from ..layers import hip_ops as H
-from ..layers import mx_guard, operand_cache
+from ..layers import mx_guard, operand_cache, precision as P
 from ..structures import Boxes, ImageList, Instances, ShapeSpec
 from .class_heads import DataAwareFeaturesHead
 from .fast_rcnn_open_vocabulary import segment_offsets
@@ -69,12 +69,9 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         self._mean, self._std = [float(v) for v in pixel_mean], [float(v) for v in pixel_std]
         self.logger = logging.getLogger(__name__)
         self.classifier = None
-        # MODEL.HIP.PRECISION = "parity_train": the heads' backward keeps the hi/lo split (layers/functions.py)
-        self.backward_split = bool(cfg is not None and cfg.MODEL.HIP.PRECISION in ("parity_train", "parity_mx_train"))
-        # "parity_mx" (round 6): the parity forward with the res4 / res5 convs and the box head's FC layers on the block-scaled
-        # f16mx kernels (layers/hip_ops.py:mx_mode); every module sees "parity", this flag selects the kernels
-        # "parity_mx_train": both flags -- the f16mx forward, and input-gradient contractions that keep the hi/lo split
-        self.mx = bool(cfg is not None and cfg.MODEL.HIP.PRECISION in ("parity_mx", "parity_mx_train"))
+        # MODEL.HIP.PRECISION (layers/precision.py:TABLE): the modules see the record's forward name, the entry points enter
+        # its x3 mode, f16mx selection and backward split (_entered).  Without a cfg: as the backbone's precision string says
+        self.hip_precision = P.of(cfg.MODEL.HIP.PRECISION if cfg is not None else getattr(backbone, "precision", "bf16"))
         # MODEL.HIP.MX_RANGE_GUARD: None = "off" (no audit is ever launched); refused for a precision without f16mx operands
         self.mx_guard = mx_guard.from_config(cfg) if cfg is not None else None
         if self.mx_guard is not None:
@@ -189,13 +186,10 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
             return self.inference(batched_inputs, classifier=classifier)
         return self.forward_trainable(self.forward_frozen(batched_inputs))
 
-    @property
-    def x3(self):
-        """MODEL.HIP.PRECISION "bf16x3" / "bf16x3f": fp32 tensors, contractions on the bf16 MFMA kernels over hi/lo-split
-        operands (layers/hip_ops.py:x3_mode; "f" = in the forward pass only) -- the fast modes that keep the north star's
-        1e-3 logit bound.  "parity" ("x2"): the forward split on bf16x2 activations (hip_ops.X2), produced by the kernels
-        themselves -- no stand-alone split passes, no fp32 activation traffic -- and a plain bf16 backward."""
-        return {"bf16x3": "full", "bf16x3f": "fwd", "parity": "x2"}.get(getattr(self.backbone, "precision", "bf16"), False)
+    # the record's fields under the names the trainer, the tools and the tests read
+    x3 = property(lambda self: self.hip_precision.x3)
+    mx = property(lambda self: self.hip_precision.mx)
+    backward_split = property(lambda self: self.hip_precision.bwd_split)
 
     @property
     def mx_on(self):
@@ -203,9 +197,13 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         g = getattr(self, "mx_guard", None)
         return bool(getattr(self, "mx", False)) and not (g is not None and g.fallen_back)
 
-    def _guarded(self):
-        """Context of every model entry point: this model's range guard is the calling thread's active one."""
-        return mx_guard.active(getattr(self, "mx_guard", None))
+    @contextlib.contextmanager
+    def _entered(self, *, mx=None, bwd_split=False, guard=True):
+        """Context of a model entry point: the precision's state on the calling thread (mx: the f16mx kernels, mx_on unless
+        given; bwd_split: the record's, the trainable part only) and, with guard, this model's range guard as its active one."""
+        with P.scope(self.hip_precision, mx=self.mx_on if mx is None else mx, bwd_split=bwd_split and self.backward_split), \
+                (mx_guard.active(getattr(self, "mx_guard", None)) if guard else contextlib.nullcontext()):
+            yield
 
     def mx_guard_end_step(self, updated=True):
         """End of an ARMED training step: audit the f16mx operands of the trained weights (after the step's update, the bytes
@@ -223,18 +221,16 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
 
     @torch.no_grad()
     def forward_frozen(self, batched_inputs):
-        with H.x3_mode(self.x3), H.mx_mode(self.mx_on), self._guarded():
+        with self._entered():
             return self._forward_frozen(batched_inputs)
 
     def forward_trainable(self, st):
-        from ..layers.functions import backward_split
-
         if self.backward_split and getattr(self, "mx", False) and getattr(self.backbone, "has_trainable_stage", False):
             raise NotImplementedError(
                 'MODEL.HIP.PRECISION "parity_mx_train" needs a frozen backbone (MODEL.BACKBONE.FREEZE_AT = 5, as in every '
                 "shipped WSR config): its split input gradients stop at the pooled tensor, and a trainable stage would "
                 'continue them through convolution backwards that keep no hi/lo split -- use "parity_train" or "parity_mx"')
-        with H.x3_mode(self.x3), backward_split(self.backward_split), H.mx_mode(self.mx_on), self._guarded():
+        with self._entered(bwd_split=True):
             return self._forward_trainable(st)
 
     @torch.no_grad()
@@ -244,7 +240,7 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
             pre()
         g = getattr(self, "mx_guard", None)
         if g is None or not self.mx_on:
-            with H.x3_mode(self.x3), H.mx_mode(self.mx_on):
+            with self._entered(guard=False):
                 return self._inference(batched_inputs, detected_instances, do_postprocess, classifier)
         # MODEL.HIP.MX_RANGE_GUARD: every inference call is audited; the table is read after the eval tail's own host read
         # (the detections' counts), so the poll waits for nothing
@@ -252,7 +248,7 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         g.reset()
         counter = self.roi_heads.iter_test
         try:
-            with H.x3_mode(self.x3), H.mx_mode(True), self._guarded():
+            with self._entered(mx=True):
                 out = self._inference(batched_inputs, detected_instances, do_postprocess, classifier)
             verdict = g.settle(g.poll())
         finally:
@@ -261,7 +257,7 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
             return out
         # THIS batch again on the bf16x2 kernels ("parity": bf16 has fp32's exponent range); sticky -- mx_on is False from now on
         self.roi_heads.iter_test = counter
-        with H.x3_mode(self.x3), H.mx_mode(False):
+        with self._entered(mx=False, guard=False):
             return self._inference(batched_inputs, detected_instances, do_postprocess, classifier)
 
     def _forward_frozen(self, batched_inputs):

@@ -25,8 +25,8 @@ from ..layers import carrier
 from ..layers import functions as Fn
 from ..layers import hip_ops as H
 from ..layers import mx_guard
+from ..layers import precision as P
 from ..structures import Boxes, ImageList, Instances, ShapeSpec
-from .backbone import forward_precision
 from .box_head import build_box_head
 from .class_heads import OpenVocabularyClassifier
 from .fast_rcnn_open_vocabulary import (InstanceRefinementOutputLayers, ObjectMiningOutputLayers,
@@ -156,13 +156,13 @@ class WSOVODROIHeads(ROIHeads):
 
     @property
     def compute_dtype(self):
-        return torch.bfloat16 if self.precision == "bf16" else torch.float32
+        return P.of(self.precision).compute_dtype
 
     @property
     def pool_dtype(self):
         """What the pooler writes: the compute dtype, bf16x2 (hip_ops.X2) under the "parity" precision, unit-scale f16mx
         (hip_ops.MX) under "parity_mx"."""
-        return H.X2 if H.x3_active() == "x2" else self.compute_dtype
+        return H.X2 if H.x2_active() else self.compute_dtype
 
     MX_MIN_ROWS = int(os.environ.get("WSOVOD_MX_MIN_ROWS", "4096"))
 
@@ -226,7 +226,7 @@ class WSOVODROIHeads(ROIHeads):
             "positive_sample_fractions": cfg.WSOVOD.SAMPLING.POSITIVE_FRACTION,
             "cls_agnostic_bbox_known": cfg.WSOVOD.CLS_AGNOSTIC_BBOX_KNOWN, "pooler_type": pooler_type,
             "rpn_on": cfg.MODEL.PROPOSAL_GENERATOR.NAME != "PrecomputedProposals", "metadata": None,
-            "precision": forward_precision(cfg.MODEL.HIP.PRECISION),
+            "precision": P.of(cfg.MODEL.HIP.PRECISION).forward,
         }
 
     # ------------------------------------------------------------------------------
@@ -304,14 +304,14 @@ class WSOVODROIHeads(ROIHeads):
         box_features = self.box_head(box_features)
         if self.pooler_type == "ROILoopPool":  # contextlocnet: the neck ran on region, frame and context rows
             parts = list(torch.chunk(box_features, 3, dim=0))
-            if H.x3_active() == "x2":
+            if H.x2_active():
                 # "parity" / "parity_mx": the neck's output is a bf16x2 carrier whose 32-value groups run along a row, so a
                 # block of rows is a carrier of the same format -- said so, torch drops the tag on a slice
                 parts = [carrier.like(box_features, q) for q in parts]
             if data_aware_features is not None:
                 nums = [len(p) for p in proposals]
                 daf = data_aware_features.to(torch.float32)
-                if H.x3_active() == "x2":
+                if H.x2_active():
                     # torch arithmetic cannot read a carrier: the group-row add of the one-output path, once per part
                     dev = box_features.device
                     if daf.size(0) == len(proposals) and daf.size(0) != sum(nums):
@@ -400,7 +400,7 @@ class WSOVODROIHeads(ROIHeads):
         hids = []
         for k in range(self.refine_K):
             l1 = self.box_refinery[k].cls.projection[0]
-            heads.append((l1.weight, l1.bias, True, H.X2 if H.x3_active() == "x2" else None))  # feeds the 2nd projection
+            heads.append((l1.weight, l1.bias, True, H.X2 if H.x2_active() else None))  # feeds the 2nd projection
             hids.append(len(heads) - 1)
         outs = Fn.linear_group(box_features, heads, joins=joins)
         return [outs[0]] + [(outs[hid], outs[reg] if reg is not None else None) for hid, reg in zip(hids, regs)]

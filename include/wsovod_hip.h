@@ -513,6 +513,30 @@ int wsovod_f16mx_from_bf16x2(const void* src, void* dst, long long n, wsovod_str
 int wsovod_gemm_f16mx(const wsovod_gemm_desc* d, const unsigned char* a_scale, int a_segments, const unsigned char* b_scale,
                       int b_segments, void* c_bf16, long long ld_c_bf16, wsovod_stream_t stream);
 
+/* Branch-batched implicit-GEMM convolution (additive entries: the ABI version stays).  ONE launch of the 256 x 256 conv tile
+ * runs the SAME 3x3 / stride-1 filter at up to four dilations -- the shared-weight branches of the reference's MRRP blocks
+ * (wsovod/modeling/backbone/vgg_mrrp.py:128-251: `conv(x_b, dilation = d_b)` per branch, `torch.cat` along N).
+ *   d      : as for wsovod_gemm_nt / wsovod_gemm_f16mx with conv = 1; geom.n_img = the PER-BRANCH image count N, d->M =
+ *            N * Ho * Wo (one branch's rows), geom.KH = KW = 3, stride 1, Ho = H, Wo = W; geom.dil / geom.pad are ignored
+ *   br     : n_branch (1 - 4) branches with pad[b] == dil[b]; shared_input = 1: A is ONE (N, H, W, Cin) map read by every
+ *            branch, 0: A is (n_branch * N, H, W, Cin), branch-major
+ *   C      : (n_branch * N, Ho, Wo, Cout) branch-major = torch.cat([conv(x_b, dilation = d_b) for b]); rows of ldc values
+ * Epilogue: bias + ReLU (alpha 1; no residual, shortcut, dropout).  No tile straddles two branches (each branch's rows are
+ * tiled on their own), no split-K: every output element is the single-launch tile's of the single-dilation entry, bit for bit.
+ * The n_branch * N input as a whole must stay below the 2 GiB buffer-addressing limit.
+ *   wsovod_gemm_conv_branches        dtype_in = WSOVOD_BF16X2 (the lean two-phase 8-wavefront tile), C in WSOVOD_BF16X2 or
+ *                                    WSOVOD_F32; any other dtype_in is WSOVOD_ERR_UNSUPPORTED (one wsovod_gemm_nt per branch)
+ *   wsovod_gemm_f16mx_conv_branches  unit-scale f16mx input, f16mx weights with b_scale / b_segments as for wsovod_gemm_f16mx;
+ *                                    C in WSOVOD_F16MX, WSOVOD_BF16X2 or WSOVOD_F32 */
+typedef struct {
+  int n_branch;
+  int dil[4], pad[4];
+  int shared_input;
+} wsovod_conv_branches;
+int wsovod_gemm_conv_branches(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream);
+int wsovod_gemm_f16mx_conv_branches(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, const unsigned char* b_scale,
+                                    int b_segments, wsovod_stream_t stream);
+
 /* Greedy non-maximum suppression over G independent segments of boxes that are already sorted by
  * descending score inside each segment.  Replaces torchvision.ops.nms / batched_nms (un-vendored; SURVEY
  * Appendix A) at the reference's call sites: find_top_rpn_proposals (proposal_utils.py:123; one segment per

@@ -46,6 +46,11 @@ class GemmDesc(C.Structure):
     ]
 
 
+class ConvBranches(C.Structure):
+    """wsovod_conv_branches (include/wsovod_hip.h)."""
+    _fields_ = [("n_branch", C.c_int), ("dil", C.c_int * 4), ("pad", C.c_int * 4), ("shared_input", C.c_int)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_longlong), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -120,6 +125,8 @@ SIGNATURES = {
     "wsovod_f16mx_encode_with": [_P, _L, _I, _I, _P, _L, _P, _P, _P],
     "wsovod_f16mx_from_bf16x2": [_P, _P, _L, _P],
     "wsovod_gemm_f16mx": [_P, _P, _I, _P, _I, _P, _L, _P],
+    "wsovod_gemm_conv_branches": [C.POINTER(GemmDesc), C.POINTER(ConvBranches), _P],
+    "wsovod_gemm_f16mx_conv_branches": [C.POINTER(GemmDesc), C.POINTER(ConvBranches), _P, _I, _P],
     "wsovod_mask_transpose_ex": [_P, _L, _I, _P, _L, _I, _I, _I, _F, _P, _L, _P, _L, _I, _P, _P],
     "wsovod_bf16x2_encode": [_P, _L, _I, _I, _P, _L, _P],
     "wsovod_bf16x2_decode": [_P, _L, _I, _I, _P, _L, _P],

@@ -1980,8 +1980,26 @@ int auto_tile(int M, int N) {
 }  // namespace wsovod_gemm
 using namespace wsovod_gemm;
 
-extern "C" int wsovod_gemm_nt(const wsovod_gemm_desc* d, wsovod_stream_t stream) {
+// br != NULL: the branch-batched conv of wsovod_gemm_conv_branches (d->M, geom.n_img: ONE branch's)
+static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream) {
   WS_CHECK_ARG(d != nullptr, "wsovod_gemm_nt: null descriptor");
+  if (br) {
+    WS_CHECK_ARG(br->n_branch >= 1 && br->n_branch <= 4, "wsovod_gemm_conv_branches: n_branch=%d must be 1 - 4", br->n_branch);
+    if (d->dtype_in != WSOVOD_BF16X2) {
+      wsovod::set_error("wsovod_gemm_conv_branches: the one-launch form exists for bf16x2 operands (and f16mx: "
+                        "wsovod_gemm_f16mx_conv_branches); other operand types run one wsovod_gemm_nt per branch");
+      return WSOVOD_ERR_UNSUPPORTED;
+    }
+    WS_CHECK_ARG(d->conv && !d->A2 && !d->residual && d->dropout_p == 0.f && d->C && !d->Ct && !d->row_scale && !d->group_add &&
+                     !d->mask_src && !d->accumulate && !d->geom.pool && d->alpha == 1.0f,
+                 "wsovod_gemm_conv_branches: a conv with the bias + ReLU epilogue only");
+    WS_CHECK_ARG(d->geom.KH == 3 && d->geom.KW == 3 && d->geom.stride == 1 && d->geom.Ho == d->geom.H && d->geom.Wo == d->geom.W &&
+                     d->geom.Cin % 32 == 0,
+                 "wsovod_gemm_conv_branches: 3x3, stride 1, output of the input's size, Cin a multiple of 32");
+    for (int b = 0; b < br->n_branch; ++b)
+      WS_CHECK_ARG(br->dil[b] >= 1 && br->pad[b] == br->dil[b], "wsovod_gemm_conv_branches: branch %d needs pad == dil >= 1", b);
+    WS_CHECK_ARG(d->dtype_c == WSOVOD_BF16X2 || d->dtype_c == WSOVOD_F32, "wsovod_gemm_conv_branches: the output is bf16x2 or fp32");
+  }
   WS_CHECK_ARG(d->dtype_in == WSOVOD_F32 || d->dtype_in == WSOVOD_BF16 || d->dtype_in == WSOVOD_BF16X2,
                "wsovod_gemm_nt: bad dtype_in %d", d->dtype_in);
   const bool x2 = d->dtype_in == WSOVOD_BF16X2;  // bf16x2 operands = bf16 matrices of twice the length for the kernels
@@ -2084,6 +2102,16 @@ extern "C" int wsovod_gemm_nt(const wsovod_gemm_desc* d, wsovod_stream_t stream)
                "wsovod_gemm_nt: a bf16x2 residual needs N and ldr multiples of 32");
   const double flops = (x2 ? 6.0 : 2.0) * d->M * d->N * d->K;  // bf16x2: three bf16 MFMA products per value pair
   hipStream_t s = (hipStream_t)stream;
+  if (br) {  // the 2 GiB limit is kept for the WHOLE n_branch * N operand, with the largest branch's border in front
+    int pmax = 0;
+    for (int b = 0; b < br->n_branch; ++b) pmax = std::max(pmax, br->pad[b]);
+    WS_CHECK_ARG(a.a_bytes * (br->shared_input ? 1 : br->n_branch) + (long long)(pmax * a.W + pmax) * a.Cin * 2 < (1ll << 31) &&
+                     (long long)d->M * br->n_branch < (1ll << 31),
+                 "wsovod_gemm_conv_branches: the n_branch * N input exceeds the 2 GiB buffer-addressing limit");
+    const double wbytes = (double)d->N * d->K * 4.0;
+    return launch_gemm256_8ph_branches(a, br->n_branch, br->dil, br->pad, br->shared_input != 0, s, flops * br->n_branch,
+                                       (bytes - wbytes) * br->n_branch + wbytes);
+  }
   if (d->conv && d->tile_hint == 0 && d->dtype_in == WSOVOD_BF16 && a.Cin == 64 && d->N == 64 && a.KH == 3 &&
       a.KW == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.Ho == a.H && a.Wo == a.W && d->C && !d->Ct && !d->A2 &&
       !d->row_scale && !d->group_add && !d->mask_src && !d->accumulate && d->dropout_p == 0.f) {
@@ -2270,4 +2298,11 @@ extern "C" int wsovod_gemm_nt(const wsovod_gemm_desc* d, wsovod_stream_t stream)
   if (d->dtype_in == WSOVOD_BF16)
     return d->conv ? dispatch_tile<bf16_t, true>(a, tile, s, flops, bytes) : dispatch_tile<bf16_t, false>(a, tile, s, flops, bytes);
   return d->conv ? dispatch_tile<float, true>(a, tile, s, flops, bytes) : dispatch_tile<float, false>(a, tile, s, flops, bytes);
+}
+
+extern "C" int wsovod_gemm_nt(const wsovod_gemm_desc* d, wsovod_stream_t stream) { return gemm_nt_impl(d, nullptr, stream); }
+
+extern "C" int wsovod_gemm_conv_branches(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream) {
+  WS_CHECK_ARG(br, "wsovod_gemm_conv_branches: null branch descriptor");
+  return gemm_nt_impl(d, br, stream);
 }

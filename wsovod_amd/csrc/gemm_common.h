@@ -53,6 +53,15 @@ struct GemmArgs {
   long long a2_bytes;
 };
 
+// The branch-batched conv (wsovod_gemm_conv_branches): the tile grid is n_branch stacks of tiles_per_branch row tiles, stack
+// b convolving with dil[b] / pad[b] on input A + b * a_branch_bytes (0: one shared input) into C + b * c_branch_bytes; M and
+// a_bytes are ONE branch's, so no tile straddles two branches
+struct GemmBrArgs : GemmArgs {
+  int tiles_per_branch;
+  int dil[4], pad[4];
+  long long a_branch_bytes, c_branch_bytes;
+};
+
 template <typename T>
 struct Traits;
 template <>
@@ -179,5 +188,8 @@ __device__ __forceinline__ void epilogue_store4(const GemmArgs& p, int m, int nb
 // x3: bf16x2 operands (three-MFMA products); merged: the two-phase form of the K-step (tile_hint 2256256)
 int launch_gemm256_8ph(const GemmArgs& a, bool conv, hipStream_t s, double flops, double bytes, bool allow_split = false,
                        bool x3 = false, bool merged = false);
+// the lean two-phase bf16x2 conv tile over n_branch dilations in ONE launch (a.M, a.a_bytes: one branch's)
+int launch_gemm256_8ph_branches(const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input,
+                                hipStream_t s, double flops, double bytes);
 
 }  // namespace wsovod_gemm

@@ -11,7 +11,7 @@ import threading
 import torch
 
 from .. import _lib
-from .._lib import BF16, BF16X2, BF16X2P, F16MX, F32, NCHW, NHWC, GemmDesc, check, dtype_code, lib, ptr, require_gpu, stream
+from .._lib import BF16, BF16X2, BF16X2P, F16MX, F32, NCHW, NHWC, ConvBranches, GemmDesc, check, dtype_code, lib, ptr, require_gpu, stream
 from . import carrier, operand_cache
 from .precision import mx_active, mx_mode, x2_active, x3_active, x3_mode  # noqa: F401 -- the modes' state and scopes, re-exported
 
@@ -567,6 +567,63 @@ def gemm_mx(A, a_scale, B, b_scale, *, bias=None, relu=False, dropout_p=0.0, dro
                                   int(b_scale.shape[1]), ptr(out_bf16), 0 if out_bf16 is None else _ld(out_bf16), stream()),
           "gemm_f16mx")
     return carrier.tag(out, out_dtype, out_bf16 if out_dtype == MX else None) if out_dtype in (X2, MX) else out
+
+
+def conv_branches(A, B, geom, dilations, *, shared_input, b_scale=None, bias=None, relu=False, out_dtype=None, out=None):
+    """The same 3x3 / stride-1 filter at up to four dilations in ONE launch (wsovod_gemm_conv_branches, or with b_scale its
+    f16mx twin wsovod_gemm_f16mx_conv_branches).  A: the NHWC bf16x2 / unit-scale f16mx input -- ONE (N, H, W, Cin) map
+    with shared_input, else (len(dilations) * N, H, W, Cin) branch-major; B: the encoded (Cout, 9 Cin) weight; geom: the
+    geometry dict of gemm_nt with n_img = the per-branch N.  Returns the (len(dilations) * N * H * W, Cout) branch-major
+    output in out_dtype (X2, MX -- f16mx operands only -- or float32): torch.cat of the per-dilation convs.  out: an optional
+    float32-typed (>= len(dilations) * N * H * W, Cout) buffer whose leading rows receive it (returned as that view)."""
+    require_gpu(A, B, b_scale, bias, out)
+    mx = b_scale is not None
+    carrier.refuse("conv_branches", (A, B), reads=(MX,) if mx else ())
+    nb = len(dilations)
+    if not 1 <= nb <= 4:
+        raise RuntimeError(f"wsovod_hip conv_branches: {nb} branches (1 - 4 per launch)")
+    if A.dtype != torch.float32 or B.dtype != torch.float32 or not A.is_contiguous():
+        raise RuntimeError("wsovod_hip conv_branches: NHWC-contiguous bf16x2 / f16mx carriers (float32-typed)")
+    d = GemmDesc()
+    d.dtype_in = F16MX if mx else BF16X2
+    d.N, d.K = B.size(0), B.size(1)
+    d.B, d.ldb = B.data_ptr(), _ld(B)
+    g = d.geom
+    for k, v in geom.items():
+        setattr(g, k, int(v))
+    g.dil = g.pad = int(dilations[0])
+    d.conv = 1
+    d.M = g.n_img * g.Ho * g.Wo
+    if A.numel() != (1 if shared_input else nb) * g.n_img * g.H * g.W * g.Cin:
+        raise RuntimeError("wsovod_hip conv_branches: the input is (N, H, W, Cin) when shared, else (n_branch * N, H, W, Cin)")
+    d.A, d.lda = A.data_ptr(), g.Cin
+    out_dtype = out_dtype or (MX if mx else X2)
+    if out_dtype == MX and not mx:
+        raise RuntimeError("wsovod_hip conv_branches: an f16mx output needs f16mx operands")
+    if out is None:
+        out = torch.empty((nb * d.M, d.N), dtype=storage_dtype(out_dtype), device=A.device)
+    elif out.dtype != storage_dtype(out_dtype) or out.dim() != 2 or out.size(0) < nb * d.M or out.size(1) != d.N:
+        raise RuntimeError("wsovod_hip conv_branches: `out` must hold (n_branch * N * H * W, Cout) rows of the output format")
+    else:
+        out = out[:nb * d.M]
+    d.C, d.ldc, d.dtype_c = out.data_ptr(), _ld(out), fmt_code(out_dtype)
+    d.alpha = 1.0
+    if bias is not None:
+        if bias.dtype != torch.float32:
+            raise RuntimeError("wsovod_hip conv_branches: bias must be fp32")
+        d.bias = bias.data_ptr()
+    d.relu = int(bool(relu))
+    br = ConvBranches()
+    br.n_branch, br.shared_input = nb, int(bool(shared_input))
+    for b, dl in enumerate(dilations):
+        br.dil[b] = br.pad[b] = int(dl)
+    if mx:
+        assert b_scale.dtype == torch.uint8 and b_scale.is_contiguous()
+        check(lib().wsovod_gemm_f16mx_conv_branches(C.byref(d), C.byref(br), ptr(b_scale), int(b_scale.shape[1]), stream()),
+              "gemm_f16mx_conv_branches")
+    else:
+        check(lib().wsovod_gemm_conv_branches(C.byref(d), C.byref(br), stream()), "gemm_conv_branches")
+    return carrier.tag(out, out_dtype) if out_dtype in (X2, MX) else out
 
 
 MX_WEIGHT_HEADROOM = 1  # binades between a trained weight's largest magnitude at its first encode and the q plane's 256

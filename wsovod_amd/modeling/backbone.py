@@ -164,7 +164,7 @@ def hip_conv(x, conv, relu=False, residual=None, pool2=False, shortcut=None, out
             out = H.gemm_mx(x, None, wm, ws, conv=geom, bias=b, relu=relu, residual=res2d,
                             residual_fmt=H.MX if res2d is not None else None, out_dtype=fmt)
         if fmt == H.MX:
-            mx_guard.audit(conv, out)
+            mx_guard.audit(getattr(conv, "audit_site", conv), out)  # (a per-call view of a conv names the module itself)
         return out.view(N, Ho, Wo, conv.out_channels)  # (a whole view of what gemm_mx tagged)
     if H.x2_active():
         # x (and residual / shortcut input) are bf16x2 maps; three-MFMA products on the bf16x2 weights; the output is

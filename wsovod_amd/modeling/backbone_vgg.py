@@ -107,7 +107,7 @@ class VGG16(FrozenForwardMixin, nn.Module):
         self._out_feature_strides, self._out_feature_channels = {}, {}
         self.stage_names, self.stages = [], []
         for name, kw, stride in plan:
-            stage = nn.Sequential(PlainBlock(**kw))
+            stage = nn.Sequential(self._make_block(name, kw))
             self.add_module(name, stage)
             self.stage_names.append(name)
             self.stages.append(stage)
@@ -122,6 +122,10 @@ class VGG16(FrozenForwardMixin, nn.Module):
             assert f in self.stage_names, "Available children: {}".format(", ".join(self.stage_names))
         self._emit_fp32_from(self.stages[-1][0])
         self.freeze(freeze_at)
+
+    def _make_block(self, name, kw):
+        """The one block of stage `name` (backbone_vgg_mrrp.py: the MRRP plain5)."""
+        return PlainBlock(**kw)
 
     def freeze(self, freeze_at=0):
         for idx, stage in enumerate(self.stages, start=1):

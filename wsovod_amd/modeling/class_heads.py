@@ -111,8 +111,7 @@ class DataAwareFeaturesHead(nn.Module):
     def __init__(self, input_shape, *, datasets_prototype_num: int = 5, features_dim: int = 512,
                  cls_in_features: List[str], mrrp_on: bool = False, mrrp_num_branch: int = 3):
         super().__init__()
-        if mrrp_on:
-            raise NotImplementedError("MRRP is off in every WSR config (out of hot-path scope)")
+        self.mrrp_on, self.mrrp_num_branch = bool(mrrp_on), int(mrrp_num_branch)
         self.in_features = self.cls_in_features = cls_in_features
         self.features_dim = features_dim
         in_channels = [input_shape[f].channels for f in self.in_features]
@@ -143,7 +142,14 @@ class DataAwareFeaturesHead(nn.Module):
                 nhwc = f.permute(0, 2, 3, 1)
             else:
                 nhwc = f.permute(0, 2, 3, 1).contiguous()
-            gaps.append(Fn.global_avgpool_nhwc(nhwc))  # (differentiable when a backbone stage is trainable)
+            gap = Fn.global_avgpool_nhwc(nhwc)  # (differentiable when a backbone stage is trainable)
+            if self.mrrp_on:
+                # data_aware_features_head.py:110-111 averages the branch maps before the GAP; by linearity that is the mean of
+                # the per-branch GAP rows of the branch-major (num_branch * N, ...) map
+                if gap.size(0) % self.mrrp_num_branch:
+                    raise RuntimeError(f"MODEL.MRRP.MRRP_ON: {gap.size(0)} map images are not NUM_BRANCH = {self.mrrp_num_branch} stacks")
+                gap = gap.view(self.mrrp_num_branch, -1, gap.size(1)).mean(0)
+            gaps.append(gap)
         return gaps
 
     def from_stats(self, gaps):

@@ -82,6 +82,13 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
     @classmethod
     def from_config(cls, cfg):
         backbone = build_backbone(cfg)
+        stacked, branches = getattr(backbone, "mrrp_stacked", False), getattr(backbone, "mrrp_num_branch", 1)
+        if cfg.MODEL.MRRP.MRRP_ON and not stacked:
+            raise NotImplementedError(f"MODEL.MRRP.MRRP_ON with {cfg.MODEL.BACKBONE.NAME}: the heads expect an MRRP backbone's "
+                                      "branch-major map (built: build_mrrp_vgg_backbone with plain5 in MRRP_STAGE)")
+        if not cfg.MODEL.MRRP.MRRP_ON and stacked:
+            raise NotImplementedError(f"{cfg.MODEL.BACKBONE.NAME} stacks {branches} MRRP branches along N but MODEL.MRRP.MRRP_ON is "
+                                      "False: the heads would pool every box from branch 0")
         return {
             "cfg": cfg, "backbone": backbone,
             "data_aware_head": DataAwareFeaturesHead(cfg, backbone.output_shape())

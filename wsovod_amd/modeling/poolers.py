@@ -125,13 +125,15 @@ class ROIPooler(nn.Module):
         self.canonical_box_size = canonical_box_size
 
     def forward(self, x: List[torch.Tensor], box_lists: List[Boxes], level_ids=None, roi_scale=None, out_dtype=None,
-                rois=None):
-        """rois: optional precomputed pooler-format boxes of `box_lists` (single-level poolers only)."""
+                rois=None, branches=1):
+        """rois: optional precomputed pooler-format boxes of `box_lists` (single-level poolers only).  branches: the map holds
+        `branches` stacks of the images along N (an MRRP backbone's output) and `rois` carry the stacked batch index."""
         num_level_assignments = len(self.level_poolers)
         assert isinstance(x, list) and isinstance(box_lists, list), "Arguments to pooler must be lists"
         assert len(x) == num_level_assignments, \
             "unequal value, num_level_assignments={}, but x is list of {} Tensors".format(num_level_assignments, len(x))
-        assert len(box_lists) == x[0].size(0), \
+        assert branches == 1 or (rois is not None and num_level_assignments == 1), "a branch-major map needs routed rois"
+        assert len(box_lists) * branches == x[0].size(0), \
             "unequal value, x[0] batch dim 0 is {}, but box_list has length {}".format(x[0].size(0), len(box_lists))
         if len(box_lists) == 0:
             return torch.zeros((0, x[0].shape[1]) + self.output_size, device=x[0].device, dtype=x[0].dtype)

@@ -221,7 +221,8 @@ class WSOVODRPN_V2(nn.Module):
                  smooth_l1_beta: float = 0.0, mrrp_on: bool = False, mrrp_num_branch: int = 3, mrrp_fast: bool = False):
         super().__init__()
         if mrrp_on:
-            raise NotImplementedError("MRRP is off in every WSR config (out of hot-path scope)")
+            raise NotImplementedError("the MRRP RPN (per-branch anchors, per-level top-k, level_id * 1000 + anchor_id) is the next step "
+                                      "after the MRRP VGG backbone and heads: MODEL.MRRP.MRRP_ON runs with precomputed proposals only")
         if box_reg_loss_type != "smooth_l1":
             raise NotImplementedError(f"RPN.BBOX_REG_LOSS_TYPE={box_reg_loss_type}: shipped configs use smooth_l1")
         self.in_features = in_features

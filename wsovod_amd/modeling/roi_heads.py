@@ -10,7 +10,7 @@ append_background=True, file_names=None, loaded_proposals=None)` and return valu
 What is on the HIP path: RoI pooling with the fused objectness scale, the neck, object mining,
 pseudo-GT mining + proposal labelling (one kernel, no host syncs, replacing the python list
 comprehensions of get_pgt_top_k :1043-1343 and label_and_sample_proposals_wsl :1722-1825) and the
-instance-refinement branch.  Out of scope (raise): MRRP, MIST
+instance-refinement branch.  Out of scope (raise): MIST
 refinement, in-loop SAM box refinement, `_vis_*` debug dumps.
 """
 import inspect
@@ -111,6 +111,21 @@ class PseudoTargets:
         return iter(self._materialise())
 
 
+def mrrp_route_rois(rois, level_ids, num_images, num_branch):
+    """Pooler-format rois (R, 5) [image n, box] -> the same with batch index (level_ids // 1000) * num_images + n: box r then
+    pools from branch level_ids[r] // 1000 of a branch-major (num_branch * num_images, ...) map -- the reference's
+    `ROIPooler.forward(level_ids=...)` over the chunked map (roi_heads.py:722-731) as an index rewrite.  A branch outside
+    [0, num_branch) raises where the ids are host-resident; device-resident ids are clamped into the range (no host read in
+    the step; the reference's `==` mask would leave such a box's features zero, and no generator of this tree emits one)."""
+    branch = torch.div(level_ids.to(torch.int64), 1000, rounding_mode="floor")
+    if not branch.is_cuda and branch.numel() and (int(branch.min()) < 0 or int(branch.max()) >= num_branch):
+        raise ValueError(f"MRRP level_ids // 1000 must lie in [0, {num_branch}): got {int(branch.min())} .. {int(branch.max())}")
+    branch = branch.clamp(0, num_branch - 1)
+    out = rois.clone()
+    out[:, 0] += (branch * num_images).to(rois.dtype)
+    return out
+
+
 @ROI_HEADS_REGISTRY.register()
 class WSOVODROIHeads(ROIHeads):
     @configurable
@@ -126,9 +141,13 @@ class WSOVODROIHeads(ROIHeads):
                  cls_agnostic_bbox_known: bool = False, pooler_type: str = "ROIPool", rpn_on: bool = False,
                  metadata: Dict = None, precision: str = "bf16", **kwargs):
         super().__init__(**kwargs)
-        if mrrp_on or refine_mist or sam is not None or train_on_pred_boxes:
-            raise NotImplementedError("MRRP / MIST refinement / in-loop SAM / TRAIN_ON_PRED_BOXES are outside the "
+        if refine_mist or sam is not None or train_on_pred_boxes:
+            raise NotImplementedError("MIST refinement / in-loop SAM / TRAIN_ON_PRED_BOXES are outside the "
                                       "hot path (SURVEY section 2, F7)")
+        if mrrp_on and mrrp_fast:
+            raise NotImplementedError("wsovod_amd: MODEL.MRRP.TEST_BRANCH_IDX != -1 with MODEL.MRRP.MRRP_ON: every shipped "
+                                      "MRRP config runs all branches (-1)")
+        self.mrrp_on, self.mrrp_num_branch = bool(mrrp_on), int(mrrp_num_branch)
         self.in_features = self.box_in_features = box_in_features
         self.box_pooler = box_pooler
         self.box_head = box_head
@@ -275,13 +294,22 @@ class WSOVODROIHeads(ROIHeads):
         boxes = self.boxes_cat(proposals)
         rois, roi_scale = H.format_rois(boxes, segment_offsets([len(p) for p in proposals], boxes.device),
                                         H.cat_rows([x.objectness_logits for x in proposals]))
+        if self.mrrp_on:
+            # roi_heads.py:722-731 chunks the map into num_branch same-scale "levels" and pools box r from level
+            # level_ids[r] // 1000.  The branches are contiguous along N in ONE map, so the routing is the batch index
+            # branch * N + n and the single-level pooler runs once on the (num_branch * N, ...) map
+            if any(f.size(0) != self.mrrp_num_branch * len(proposals) for f in feats):
+                raise RuntimeError(f"MODEL.MRRP.MRRP_ON: the feature map holds {feats[0].size(0)} images, not NUM_BRANCH = "
+                                   f"{self.mrrp_num_branch} x {len(proposals)} (an MRRP backbone stacks its branches along N)")
+            rois = mrrp_route_rois(rois, H.cat_rows([x.level_ids for x in proposals]), len(proposals), self.mrrp_num_branch)
         # ROILoopPool: (3R, C, 7, 7) = [region | frame | context] (roi_heads.py:727-739); the scale of box r is applied to
         # its three rows inside the kernel, and fc1 sees 3R rows: that count picks the carrier
         rows = int(rois.shape[0]) * (3 if self.pooler_type == "ROILoopPool" else 1)
         Fn._WANT_HI.on = self.training and os.environ.get("WSOVOD_X2_HI", "1") != "0"  # (bf16x2 pooling only) a plain bf16 copy for fc1's dW
         try:
+            extra = {"branches": self.mrrp_num_branch} if self.mrrp_on else {}  # (the map's N is num_branch x the images)
             pooled = self.box_pooler(feats, [x.proposal_boxes for x in proposals], roi_scale=roi_scale,
-                                     out_dtype=self._pool_dtype_for(rows), rois=rois)
+                                     out_dtype=self._pool_dtype_for(rows), rois=rois, **extra)
             if H.mx_of(pooled):
                 mx_guard.audit("roi_heads.pooled", pooled)
             return pooled

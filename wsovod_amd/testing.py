@@ -12,13 +12,17 @@ _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs"
 
 
 def hot_path_cfg(depth=18, K=20, D=512, precision="bf16", pooler="ROIPool", device="cuda", weight_path=None,
-                 emb_seed=7, rpn=False, freeze_at=None, backbone="resnet"):
+                 emb_seed=7, rpn=False, freeze_at=None, backbone="resnet", mrrp=False):
     """WSOVOD_WSR_{18,50}_DC5_1x in proposals-only mode: the keys below are the values of
     /root/reference/configs/PascalVOC-Detection/{Base-RCNN-DilatedC5,WSOVOD_WSR_18_DC5_1x}.yaml
     that the hot path reads, with PROPOSAL_GENERATOR=PrecomputedProposals, BBOX_REFINE off.
-    backbone="vgg16": WSOVOD_V_16_DC5_1x instead (hot_path_vgg16.yaml; `depth` is not read)."""
+    backbone="vgg16": WSOVOD_V_16_DC5_1x instead (hot_path_vgg16.yaml; `depth` is not read); with mrrp its MRRP form
+    (hot_path_vgg16_mrrp.yaml: precomputed proposals only)."""
     cfg = get_cfg()
-    if backbone == "vgg16":
+    if mrrp:
+        assert backbone == "vgg16" and not rpn, "the MRRP hot path is the VGG16 one with precomputed proposals"
+        cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_mrrp.yaml"))
+    elif backbone == "vgg16":
         cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_rpn.yaml" if rpn else "hot_path_vgg16.yaml"))
     else:
         assert backbone == "resnet", backbone

@@ -1,4 +1,4 @@
-"""The fp64 restatement of the conv backward of a trainable stage (wsovod_amd/modeling/backbone.py: `_conv_dgrad`,
+"""The fp64 restatement of the conv backward of a trainable stage (wsovod_amd/modeling/conv_backward.py: `_conv_dgrad`,
 `_conv_wgrad`, `_block_backward`, `_stage_backward_hip`), shared by tests/test_conv_backward_ref.py (CPU) and
 tests/test_gpu_conv_backward.py.  Torch on the CPU in float64; the HIP library is never touched.
 
@@ -14,7 +14,7 @@ absolute  the same sums over |dy|, |w|, |x|, |scale| with the same 0/1 masks and
           the magnitudes of all terms of each output element.
 defect    (name, conv index | "shortcut" | None): one deliberate bug, for the sensitivity tests (DEFECTS below).
 
-Tolerances: |got - ref_as_read| <= c * u * B, u = U[cd].  The c_* functions below count c from the code of backbone.py.
+Tolerances: |got - ref_as_read| <= c * u * B, u = U[cd].  The c_* functions below count c from the code of conv_backward.py.
 """
 import torch
 import torch.nn.functional as F
@@ -31,7 +31,7 @@ DEFECTS = ("dgrad_unrotated", "w1x1_untransposed", "wgrad_no_scale", "dgrad_no_s
            "first_row_block_overwritten", "mask_from_output", "no_shortcut_dx", "pool_last_maximum")
 
 
-# ---- c: counted from backbone.py --------------------------------------------------------------------------------------
+# ---- c: counted from conv_backward.py ---------------------------------------------------------------------------------
 # One fp32 accumulation of K terms (MFMA, any order, any split) errs by at most gamma_K ~ K * 2^-24 of the sum of the
 # terms' magnitudes; the issue's rule doubles it: 2 * K * 2^-24, in units of u.  One extra fp32 operation is 2^-24 / u.
 def acc(K, cd):

@@ -1,4 +1,4 @@
-"""GPU: the HIP conv backward of a trainable stage (wsovod_amd/modeling/backbone.py: `_masked`, `_conv_dgrad`, `_conv_wgrad`,
+"""GPU: the HIP conv backward of a trainable stage (wsovod_amd/modeling/conv_backward.py: `_masked`, `_conv_dgrad`, `_conv_wgrad`,
 `_block_backward`, `_stage_backward_hip`, `_TrainableStem.backward`) against the linear fp64 reference of
 tests/conv_backward_ref.py, block by block: BasicBlocks AND the BottleneckBlocks of the WSR_50 configs.
 
@@ -94,7 +94,7 @@ _BLOCKS = {}
 
 
 def _block_case(kind, mode, gpu):
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import conv_backward as BB
 
     if (kind, mode) not in _BLOCKS:
         H = _H()
@@ -139,7 +139,7 @@ def test_the_recomputation_is_the_forward(gpu, kind, mode):
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("kind", R.BLOCK_KINDS)
 def test_block_backward_against_fp64(gpu, kind, mode):
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import conv_backward as BB
 
     H = _H()
     case = _block_case(kind, mode, gpu)
@@ -186,7 +186,7 @@ def _conv(name, gpu):
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("name", list(CONVS))
 def test_conv_dgrad_against_fp64(gpu, name, mode):
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import conv_backward as BB
 
     H = _H()
     conv, cd = _conv(name, gpu), MODES[mode][1]
@@ -207,7 +207,7 @@ def test_conv_dgrad_against_fp64(gpu, name, mode):
 @pytest.mark.parametrize("fmt", list(MODES))
 @pytest.mark.parametrize("name", list(CONVS))
 def test_conv_wgrad_against_fp64(gpu, monkeypatch, name, fmt, blocked):
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import conv_backward as BB
 
     H = _H()
     conv, cd = _conv(name, gpu), MODES[fmt][1]
@@ -247,7 +247,7 @@ STAGES = {"bottleneck": ("bottleneck_dilated_projection", "bottleneck_identity")
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("stage_name", list(STAGES))
 def test_trainable_stage_against_fp64(gpu, stage_name, mode):
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import conv_backward as BB
 
     H = _H()
     x3, cd = MODES[mode]
@@ -309,13 +309,13 @@ def test_trainable_stage_against_fp64(gpu, stage_name, mode):
 @pytest.mark.parametrize("mode", ["fp32", "parity"])
 def test_trainable_stem_against_fp64(gpu, mode):
     import torch.nn.functional as F
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import backbone as B, conv_backward as BB
 
     H = _H()
     x3, cd = MODES[mode]
     torch.manual_seed(500)
-    stem = R.seed_bn(BB.BasicStem(3, 64, norm="FrozenBN"), 501)
-    net = BB.ResNet(stem, [[R.make_block("basic_identity")]], freeze_at=0, precision=mode).to(gpu)
+    stem = R.seed_bn(B.BasicStem(3, 64, norm="FrozenBN"), 501)
+    net = B.ResNet(stem, [[R.make_block("basic_identity")]], freeze_at=0, precision=mode).to(gpu)
     img = torch.randint(0, 256, (2, 3, 32, 40), generator=torch.Generator().manual_seed(502), dtype=torch.uint8).to(gpu)
     sizes = torch.tensor([[32, 40], [32, 40]], dtype=torch.int32, device=gpu)
     mean, std = (103.53, 116.28, 123.675), (57.375, 57.12, 58.395)
@@ -327,8 +327,8 @@ def test_trainable_stem_against_fp64(gpu, mode):
     torch.cuda.synchronize()
     with torch.no_grad(), H.x3_mode(x3):
         a1 = net._stem_conv1(img, sizes, mean, std)
-        a2 = BB.hip_conv(a1, stem.conv2, relu=True)
-        a3 = BB.hip_conv(a2, stem.conv3, relu=True)
+        a2 = B.hip_conv(a1, stem.conv2, relu=True)
+        a3 = B.hip_conv(a2, stem.conv3, relu=True)
         assert same_bits(H.maxpool2x2_nhwc(a3, 2, x2=H.x2_active()), out.detach())
     h1, h2 = _hi(a1), _hi(a2)
     a1, a2, a3 = _values(a1), _values(a2), _values(a3)

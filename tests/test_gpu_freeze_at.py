@@ -1,5 +1,5 @@
 """GPU: MODEL.BACKBONE.FREEZE_AT < 5 (reference: backbone/resnet_wsl.py:530-552).  The trainable stages run their FORWARD
-on the HIP kernels; their backward (`modeling/backbone.py:_TrainableStage`) too since round 6 for the stages without a tail
+on the HIP kernels; their backward (`modeling/conv_backward.py:_TrainableStage`) too since round 6 for the stages without a tail
 pool (res4 / res5: mask passes, input gradients as implicit-GEMM convs on the rotated weights, weight gradients as the
 transposed-read contraction over im2col rows); res2 / res3 keep the torch-autograd re-evaluation (MIOpen).  Pinned to the
 REFERENCE's own step at FREEZE_AT = 4 (tests/golden/g19_freeze_at_4.npz, make_golden.py:golden_trainable_stage): the
@@ -74,7 +74,7 @@ def test_hip_conv_backward_agrees_with_the_torch_re_evaluation(gpu, monkeypatch,
     conv and blocks with an identity shortcut; at FREEZE_AT = 1 / 2 also the stages with a tail pool (res2: stride 2, fused
     into the 64-channel conv in the forward pass; res3: ZeroPad2d + stride 1) through the pool-backward kernel -- agrees in
     norm and element-wise to the precision's backward grade."""
-    from wsovod_amd.modeling import backbone as BB
+    from wsovod_amd.modeling import conv_backward as BB
 
     batch = to_inputs(gen.seeded_batch(2, 24, 20, 160, 208, seed=13))
     if freeze_at == 1:  # the weight gradients in several row blocks of patch rows (accumulated), as at large batches

@@ -994,7 +994,7 @@ def test_backbone_in_image_blocks_equals_the_single_launch_in_the_parity_precisi
 
 def _image_blocks_equal_the_single_launch(gpu, depth, precision, monkeypatch):
     from wsovod_amd.layers import hip_ops as H
-    from wsovod_amd.modeling import backbone as B
+    from wsovod_amd.modeling import conv as B
     from wsovod_amd.testing import build_hot_path_model
 
     _lower_mx_thresholds(monkeypatch, precision)

@@ -205,7 +205,7 @@ def test_parity_mx_below_its_thresholds_is_the_parity_forward(gpu):
 def test_image_blocks_equal_the_unblocked_run(gpu, precision, monkeypatch):
     """CONV_MAX_OPERAND_BYTES lowered so that the full-resolution plain1 map goes through conv1_2 in blocks of one image
     (at 800 x 600 that is the normal path from 18 images up)."""
-    from wsovod_amd.modeling import backbone as B
+    from wsovod_amd.modeling import conv as B
 
     cfg, model, sd = _build(precision)
     g = torch.Generator().manual_seed(5)

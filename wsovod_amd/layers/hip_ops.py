@@ -517,6 +517,20 @@ def mx_from_x2(src):
     return carrier.tag(out, MX)
 
 
+def _set_conv(d, A, geom, A2=None):
+    """The conv side of a GemmDesc: the geometry dict -> d.geom, M = the output pixels, A = the NHWC input with lda = Cin, and
+    the fused projection shortcut's input A2 / Cin2.  -> d.geom (the callers check what they require of A and A2)."""
+    g = d.geom
+    for k, v in geom.items():
+        setattr(g, k, int(v))
+    d.conv = 1
+    d.M = g.n_img * g.Ho * g.Wo
+    d.A, d.lda = A.data_ptr(), g.Cin
+    if A2 is not None:
+        d.A2, d.Cin2 = A2.data_ptr(), int(A2.shape[-1])
+    return g
+
+
 def gemm_mx(A, a_scale, B, b_scale, *, bias=None, relu=False, dropout_p=0.0, dropout_seed=0, dropout_seed_add=None,
             alpha=1.0, out=None, out_dtype=torch.float32, out_bf16=None, residual=None, residual_fmt=None, conv=None, A2=None):
     """C = epilogue(A B^T) on f16mx operands (mx_encode): wsovod_gemm_f16mx.  a_scale None: A is a unit-scale (activation)
@@ -530,18 +544,11 @@ def gemm_mx(A, a_scale, B, b_scale, *, bias=None, relu=False, dropout_p=0.0, dro
     d.N, d.K = B.size(0), B.size(1)
     d.B, d.ldb = B.data_ptr(), _ld(B)
     if conv is not None:
-        g = d.geom
-        for k, v in conv.items():
-            setattr(g, k, int(v))
-        d.conv = 1
-        d.M = g.n_img * g.Ho * g.Wo
-        d.A, d.lda = A.data_ptr(), g.Cin
+        _set_conv(d, A, conv, A2)
         if not A.is_contiguous():
             raise RuntimeError("wsovod_hip gemm_mx: the conv input must be NHWC-contiguous")
-        if A2 is not None:
-            if not A2.is_contiguous() or A2.numel() != d.M * A2.shape[-1]:
-                raise RuntimeError("wsovod_hip gemm_mx: the fused shortcut input must be NHWC-contiguous (n_img, Ho, Wo, Cin2)")
-            d.A2, d.Cin2 = A2.data_ptr(), int(A2.shape[-1])
+        if A2 is not None and (not A2.is_contiguous() or A2.numel() != d.M * A2.shape[-1]):
+            raise RuntimeError("wsovod_hip gemm_mx: the fused shortcut input must be NHWC-contiguous (n_img, Ho, Wo, Cin2)")
     else:
         d.M = A.size(0)
         d.A, d.lda = A.data_ptr(), _ld(A)
@@ -588,15 +595,10 @@ def conv_branches(A, B, geom, dilations, *, shared_input, b_scale=None, bias=Non
     d.dtype_in = F16MX if mx else BF16X2
     d.N, d.K = B.size(0), B.size(1)
     d.B, d.ldb = B.data_ptr(), _ld(B)
-    g = d.geom
-    for k, v in geom.items():
-        setattr(g, k, int(v))
+    g = _set_conv(d, A, geom)
     g.dil = g.pad = int(dilations[0])
-    d.conv = 1
-    d.M = g.n_img * g.Ho * g.Wo
     if A.numel() != (1 if shared_input else nb) * g.n_img * g.H * g.W * g.Cin:
         raise RuntimeError("wsovod_hip conv_branches: the input is (N, H, W, Cin) when shared, else (n_branch * N, H, W, Cin)")
-    d.A, d.lda = A.data_ptr(), g.Cin
     out_dtype = out_dtype or (MX if mx else X2)
     if out_dtype == MX and not mx:
         raise RuntimeError("wsovod_hip conv_branches: an f16mx output needs f16mx operands")
@@ -790,18 +792,12 @@ def gemm_nt(A, B, *, out=None, out_dtype=None, out_t=None, alpha=1.0, row_scale=
     d.K = B.size(1) if K is None else K
     d.B, d.ldb = B.data_ptr(), _ld(B)
     if conv is not None:
-        g = d.geom
-        for k, v in conv.items():
-            setattr(g, k, int(v))
-        d.conv = 1
-        d.M = g.n_img * g.Ho * g.Wo
-        d.A, d.lda = A.data_ptr(), g.Cin
+        _set_conv(d, A, conv, A2)
         if A2 is not None:
             require_gpu(A2)
             if A2.dtype != A.dtype or not A2.is_contiguous() or A2.numel() != d.M * A2.shape[-1]:
                 raise RuntimeError("wsovod_hip gemm: the fused shortcut input must be NHWC-contiguous (n_img, Ho, Wo, Cin2) "
                                    "in the dtype of A")
-            d.A2, d.Cin2 = A2.data_ptr(), int(A2.shape[-1])
     else:
         d.M = A.size(0) if M is None else M
         d.A, d.lda = A.data_ptr(), _ld(A)

@@ -9,10 +9,10 @@ which shrinks the map by one row and one column (vgg.py:98-99,181-184).
 
 Forward only: every shipped V_16 config freezes the whole backbone (FREEZE_AT: 5), and a trainable plain stage raises.
 
-    plain1   conv1_1 from the uint8 canvas by the stride-1 first-conv kernels (csrc/stem.hip: wsovod_stem_conv1_s1[_x2]; the
+    plain1   conv1_1 from the uint8 canvas by conv.py's first_conv at stride 1 (csrc/stem.hip: wsovod_stem_conv1_s1[_x2]; the
              fp32 / bf16x3 precisions: wsovod_stem_im2col_ex + GEMM); conv1_2 + its pool in ONE launch of the 64-channel kernel
              (the pool in its epilogue): the full-resolution 64-channel map is written once and read once
-    plain2-5 hip_conv per conv (backbone.py), the NHWC pool kernel per stage
+    plain2-5 hip_conv per conv (conv.py), the NHWC pool kernel per stage
     parity   bf16x2 maps inside, real fp32 from the last conv of plain5
     parity_mx  the trailing run of stages whose convs are >= 256 wide (plain3 on) on the f16mx kernels: the crossing is
              mx_from_x2 on the run's input, the pools inside the run are the f16mx pool (wsovod_maxpool2x2_nhwc with
@@ -23,21 +23,10 @@ from torch import nn
 
 from ..config import BACKBONE_REGISTRY
 from ..layers import hip_ops as H, mx_guard
-from .backbone import CNNBlockBase, Conv2d, FrozenForwardMixin, c2_msra_fill, forward_precision, hip_conv
+from .backbone import CNNBlockBase, FrozenForwardMixin, forward_precision
+from .conv import Conv2d, c2_msra_fill, first_conv, hip_conv
 
 __all__ = ["PlainBlock", "VGG16", "build_vgg_backbone"]
-
-
-def _im2col_weight(conv, dtype):
-    """conv1_1's folded [64][27] weight in `dtype`, zero-padded to the [64][32] operand of the im2col order; cached with
-    the fold."""
-    wq, b = conv.folded(dtype)
-    wpad = getattr(conv, "_w_im2col", None)
-    if wpad is None or wpad[0] is not wq:
-        w32 = torch.zeros((wq.size(0), 32), dtype=wq.dtype, device=wq.device)
-        w32[:, :27] = wq
-        conv._w_im2col = wpad = (wq, w32)
-    return wpad[1], b
 
 
 class PlainBlock(CNNBlockBase):
@@ -137,17 +126,9 @@ class VGG16(FrozenForwardMixin, nn.Module):
     # ---- "parity_mx" ----
     MX_FIRST = "plain3"  # the earliest stage the f16mx run may start at (the 1e-3 logit bar holds from here)
 
-    def _mx_from(self):
-        """Index of the first stage on the f16mx kernels: the trailing run of frozen stages whose every conv is at least 256
-        channels wide with whole 32-value channel groups (plain3 on); len(stages) = none."""
-        first = len(self.stages)
-        for i in range(len(self.stages) - 1, self.stage_names.index(self.MX_FIRST) - 1, -1):
-            convs = [c for b in self.stages[i].children() for c in b.convs()]
-            if not all(c.in_channels % 32 == 0 and c.out_channels % 32 == 0 and c.out_channels >= 256 for c in convs) \
-                    or any(p.requires_grad for p in self._stage_params(self.stages[i])):
-                break
-            first = i
-        return first
+    def _mx_block_ok(self, b):
+        """FrozenForwardMixin._mx_from: every conv at least 256 channels wide with whole 32-value channel groups (plain3 on)."""
+        return all(c.in_channels % 32 == 0 and c.out_channels % 32 == 0 and c.out_channels >= 256 for c in b.convs())
 
     def _mx_min_tiles(self, x, first):
         """256-row tiles of the SMALLEST conv of the f16mx run that starts with the map x (its pools shrink the later ones)."""
@@ -182,16 +163,7 @@ class VGG16(FrozenForwardMixin, nn.Module):
 
     def _conv1_1(self, images_u8, sizes, pixel_mean, pixel_std):
         """relu(conv1_1(normalised image)): (N, Hp, Wp, 64) NHWC in the precision's activation format."""
-        conv = self.stages[0][0].conv1
-        if H.x2_active():
-            w32, b = _im2col_weight(conv, torch.float32)
-            return H.stem_conv1_s1_x2(images_u8, sizes, pixel_mean, pixel_std, H.x2_cached(w32), b)
-        if self.compute_dtype == torch.bfloat16:
-            w32, b = _im2col_weight(conv, torch.bfloat16)
-            return H.stem_conv1_s1(images_u8, sizes, pixel_mean, pixel_std, w32, b)
-        a, ho, wo = H.stem_im2col_ex(images_u8, sizes, pixel_mean, pixel_std, self.compute_dtype, 1)
-        w32, b = _im2col_weight(conv, a.dtype)
-        return H.gemm_nt(a, w32, bias=b, relu=True, out_dtype=a.dtype).view(images_u8.size(0), ho, wo, conv.out_channels)
+        return first_conv(self.stages[0][0].conv1, images_u8, sizes, pixel_mean, pixel_std, 1, self.compute_dtype)
 
     def _forward_uint8(self, images_u8, sizes, pixel_mean, pixel_std):
         with torch.no_grad():

@@ -19,8 +19,9 @@ import torch
 
 from ..config import BACKBONE_REGISTRY
 from ..layers import carrier, hip_ops as H, mx_guard
-from . import backbone as B
-from .backbone import CNNBlockBase, Conv2d, c2_msra_fill, forward_precision, hip_conv, _folded_x2
+from . import conv as C
+from .backbone import CNNBlockBase, forward_precision
+from .conv import Conv2d, c2_msra_fill, conv_operand, hip_conv
 from .backbone_vgg import VGG16
 
 __all__ = ["MRRPPlainBlock", "MRRPVGG16", "build_mrrp_vgg_backbone", "hip_conv_branches"]
@@ -43,29 +44,12 @@ def branch_batched_default(mx, n_images):
     return n_images <= BATCHED_UP_TO["f16mx" if mx else "bf16x2"]
 
 
-class _Dilated:
-    """`conv` seen at dilation d (padding d): the parameter holder's folded weight at another geometry."""
-
-    def __init__(self, conv, d):
-        self.__dict__["_conv"], self.__dict__["_d"] = conv, d
-
-    def __getattr__(self, name):
-        if name in ("padding", "dilation"):
-            return self._d
-        if name == "audit_site":  # mx_guard keys its sites by object: the module, not this per-call view
-            return self._conv
-        return getattr(self._conv, name)
-
-    def __setattr__(self, name, value):  # (the operand caches live on the parameter holder)
-        setattr(self._conv, name, value)
-
-
 def _batched_images(conv, Hh, Ww, dilations):
     """Per-branch images the one-launch form takes at once: the n_branch * N operand (input or output, 4 bytes per value)
     plus the largest branch's border in front stays below the buffer-addressing limit (the C side's own check)."""
     pmax = max(dilations)
     per_image = len(dilations) * Hh * Ww * max(conv.in_channels, conv.out_channels) * 4
-    return (B.CONV_MAX_OPERAND_BYTES - (pmax * Ww + pmax) * conv.in_channels * 4) // per_image
+    return (C.CONV_MAX_OPERAND_BYTES - (pmax * Ww + pmax) * conv.in_channels * 4) // per_image
 
 
 def hip_conv_branches(x, conv, dilations, shared_input, relu=False, out_fp32=False, batched=None):
@@ -103,24 +87,20 @@ def hip_conv_branches(x, conv, dilations, shared_input, relu=False, out_fp32=Fal
                 outs.append((j - i, hip_conv_branches(xb, conv, dilations, shared_input, relu=relu, out_fp32=out_fp32, batched=True)))
             return carrier.like(outs[0][1], torch.cat([o[bi * n:(bi + 1) * n] for bi in range(nb) for n, o in outs]))
         geom = dict(n_img=N, H=Hh, W=Ww, Cin=Cin, Ho=Hh, Wo=Ww, KH=3, KW=3, stride=1, pad=dilations[0], dil=dilations[0])
-        if H.mx_of(x):
-            wq, b = conv.folded(torch.float32, cin_pad=Cin)
-            wm, ws = H.mx_cached(wq)
-            fmt = torch.float32 if out_fp32 else H.MX
-            out = H.conv_branches(x, wm, geom, dilations, shared_input=shared_input, b_scale=ws, bias=b, relu=relu, out_dtype=fmt)
-            if fmt == H.MX:
-                mx_guard.audit(conv, out)
-        else:
-            wq, b = _folded_x2(conv, cin_pad=Cin)
-            out = H.conv_branches(x, wq, geom, dilations, shared_input=shared_input, bias=b, relu=relu,
-                                  out_dtype=torch.float32 if out_fp32 else H.X2)
+        fmt = H.MX if H.mx_of(x) else H.X2
+        out_fmt = torch.float32 if out_fp32 else fmt
+        w, w_scale, b = conv_operand(conv, fmt, cin_pad=Cin)
+        out = H.conv_branches(x, w, geom, dilations, shared_input=shared_input, b_scale=w_scale, bias=b, relu=relu,
+                              out_dtype=out_fmt)
+        if out_fmt == H.MX:
+            mx_guard.audit(conv, out)
         return out.view(nb * N, Hh, Ww, conv.out_channels)  # (a whole view of what conv_branches tagged)
     # the loop: one single-dilation conv per branch (its own image blocks above 2 GiB), concatenated along N.  A batch slice is
     # not a whole view and `cat` carries no tag: slices and the output are tagged like their source (layers/carrier.py)
     parts = []
     for bi, d in enumerate(dilations):
         xb = x if shared_input else carrier.like(x, x[bi * N:(bi + 1) * N])
-        parts.append(hip_conv(xb, _Dilated(conv, int(d)), relu=relu, out_fp32=out_fp32))
+        parts.append(hip_conv(xb, conv, relu=relu, out_fp32=out_fp32, dilation=int(d)))
     return parts[0] if nb == 1 else carrier.like(parts[0], torch.cat(parts))
 
 

@@ -536,6 +536,21 @@ typedef struct {
 int wsovod_gemm_conv_branches(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream);
 int wsovod_gemm_f16mx_conv_branches(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, const unsigned char* b_scale,
                                     int b_segments, wsovod_stream_t stream);
+/* The same with the residual epilogue and 1x1 filters (additive entries again) -- the shared-weight branches of the
+ * reference's MRRP residual blocks (wsovod/modeling/backbone/resnet_wsl_mrrp.py:122-239, :373-522: conv + FrozenBN per
+ * branch, `out_b + shortcut_b`, ReLU).  Everything above holds, plus:
+ *   d->residual : added before the ReLU, exactly as wsovod_gemm_nt / wsovod_gemm_f16mx do (add, then ReLU), rows of ldr
+ *                 values in dtype_r (WSOVOD_BF16X2 or WSOVOD_F32; the f16mx entry also WSOVOD_F16MX); NULL = none.
+ *                 residual_shared = 0: (n_branch * N, Ho, Wo, Cout) branch-major, as C; residual_shared = 1: ONE
+ *                 (N, Ho, Wo, Cout) map added to every branch (block 0 of the stage: every branch read the same input, so
+ *                 its projection shortcut is computed once)
+ *   geom.KH = KW: 3 as above, or 1: the ordinary 1x1 conv of every branch's rows in one launch (br->dil / br->pad ignored),
+ *                 which with a shared residual is the Bottleneck tail conv3 + shortcut + ReLU of block 0
+ * Each is a further compilation of the tile's text under its own kernel name: the entries above keep their code. */
+int wsovod_gemm_conv_branches_ex(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, int residual_shared,
+                                 wsovod_stream_t stream);
+int wsovod_gemm_f16mx_conv_branches_ex(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, int residual_shared,
+                                       const unsigned char* b_scale, int b_segments, wsovod_stream_t stream);
 
 /* Greedy non-maximum suppression over G independent segments of boxes that are already sorted by
  * descending score inside each segment.  Replaces torchvision.ops.nms / batched_nms (un-vendored; SURVEY

@@ -127,6 +127,8 @@ SIGNATURES = {
     "wsovod_gemm_f16mx": [_P, _P, _I, _P, _I, _P, _L, _P],
     "wsovod_gemm_conv_branches": [C.POINTER(GemmDesc), C.POINTER(ConvBranches), _P],
     "wsovod_gemm_f16mx_conv_branches": [C.POINTER(GemmDesc), C.POINTER(ConvBranches), _P, _I, _P],
+    "wsovod_gemm_conv_branches_ex": [C.POINTER(GemmDesc), C.POINTER(ConvBranches), _I, _P],
+    "wsovod_gemm_f16mx_conv_branches_ex": [C.POINTER(GemmDesc), C.POINTER(ConvBranches), _I, _P, _I, _P],
     "wsovod_mask_transpose_ex": [_P, _L, _I, _P, _L, _I, _I, _I, _F, _P, _L, _P, _L, _I, _P, _P],
     "wsovod_bf16x2_encode": [_P, _L, _I, _I, _P, _L, _P],
     "wsovod_bf16x2_decode": [_P, _L, _I, _I, _P, _L, _P],

@@ -1980,10 +1980,41 @@ int auto_tile(int M, int N) {
 }  // namespace wsovod_gemm
 using namespace wsovod_gemm;
 
-// br != NULL: the branch-batched conv of wsovod_gemm_conv_branches (d->M, geom.n_img: ONE branch's)
-static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream) {
+// br != NULL: the branch-batched conv of wsovod_gemm_conv_branches (d->M, geom.n_img: ONE branch's); ex != NULL: its _ex
+// form (residual epilogue, *ex = the residual is ONE map shared by the branches; 1x1 filters next to 3x3)
+static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream, const int* ex = nullptr) {
   WS_CHECK_ARG(d != nullptr, "wsovod_gemm_nt: null descriptor");
-  if (br) {
+  wsovod_gemm_desc d1x1;
+  wsovod_conv_branches br1x1;
+  if (br && ex) {
+    WS_CHECK_ARG(br->n_branch >= 1 && br->n_branch <= 4, "wsovod_gemm_conv_branches_ex: n_branch=%d must be 1 - 4", br->n_branch);
+    if (d->dtype_in != WSOVOD_BF16X2) {
+      wsovod::set_error("wsovod_gemm_conv_branches_ex: the one-launch form exists for bf16x2 operands (and f16mx: "
+                        "wsovod_gemm_f16mx_conv_branches_ex); other operand types run one wsovod_gemm_nt per branch");
+      return WSOVOD_ERR_UNSUPPORTED;
+    }
+    WS_CHECK_ARG(d->conv && !d->A2 && d->dropout_p == 0.f && d->C && !d->Ct && !d->row_scale && !d->group_add && !d->mask_src &&
+                     !d->accumulate && !d->geom.pool && d->alpha == 1.0f,
+                 "wsovod_gemm_conv_branches_ex: a conv with the bias + residual + ReLU epilogue only");
+    const bool k3 = d->geom.KH == 3 && d->geom.KW == 3, k1 = d->geom.KH == 1 && d->geom.KW == 1;
+    WS_CHECK_ARG((k3 || k1) && d->geom.stride == 1 && d->geom.Ho == d->geom.H && d->geom.Wo == d->geom.W && d->geom.Cin % 32 == 0,
+                 "wsovod_gemm_conv_branches_ex: 3x3 or 1x1, stride 1, output of the input's size, Cin a multiple of 32");
+    WS_CHECK_ARG(!d->residual || d->dtype_r == WSOVOD_BF16X2 || d->dtype_r == WSOVOD_F32,
+                 "wsovod_gemm_conv_branches_ex: the residual is bf16x2 or fp32");
+    WS_CHECK_ARG(d->dtype_c == WSOVOD_BF16X2 || d->dtype_c == WSOVOD_F32, "wsovod_gemm_conv_branches_ex: the output is bf16x2 or fp32");
+    if (k1) {  // a 1x1 filter has no dilation: every branch runs it at dil 1 / pad 0 on its own rows
+      d1x1 = *d;
+      br1x1 = *br;
+      d1x1.geom.dil = 1;
+      d1x1.geom.pad = 0;
+      for (int b = 0; b < 4; ++b) br1x1.dil[b] = 1, br1x1.pad[b] = 0;
+      d = &d1x1;
+      br = &br1x1;
+    } else {
+      for (int b = 0; b < br->n_branch; ++b)
+        WS_CHECK_ARG(br->dil[b] >= 1 && br->pad[b] == br->dil[b], "wsovod_gemm_conv_branches_ex: branch %d needs pad == dil >= 1", b);
+    }
+  } else if (br) {
     WS_CHECK_ARG(br->n_branch >= 1 && br->n_branch <= 4, "wsovod_gemm_conv_branches: n_branch=%d must be 1 - 4", br->n_branch);
     if (d->dtype_in != WSOVOD_BF16X2) {
       wsovod::set_error("wsovod_gemm_conv_branches: the one-launch form exists for bf16x2 operands (and f16mx: "
@@ -2109,6 +2140,11 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
                      (long long)d->M * br->n_branch < (1ll << 31),
                  "wsovod_gemm_conv_branches: the n_branch * N input exceeds the 2 GiB buffer-addressing limit");
     const double wbytes = (double)d->N * d->K * 4.0;
+    if (ex) {
+      const double rbytes = d->residual ? (double)d->M * d->N * 4.0 * (*ex ? 1 : br->n_branch) : 0.0;
+      return launch_gemm256_8ph_branches_ex(a, br->n_branch, br->dil, br->pad, br->shared_input != 0, *ex != 0, s,
+                                            flops * br->n_branch, (bytes - wbytes) * br->n_branch + wbytes + rbytes);
+    }
     return launch_gemm256_8ph_branches(a, br->n_branch, br->dil, br->pad, br->shared_input != 0, s, flops * br->n_branch,
                                        (bytes - wbytes) * br->n_branch + wbytes);
   }
@@ -2305,4 +2341,10 @@ extern "C" int wsovod_gemm_nt(const wsovod_gemm_desc* d, wsovod_stream_t stream)
 extern "C" int wsovod_gemm_conv_branches(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, wsovod_stream_t stream) {
   WS_CHECK_ARG(br, "wsovod_gemm_conv_branches: null branch descriptor");
   return gemm_nt_impl(d, br, stream);
+}
+
+extern "C" int wsovod_gemm_conv_branches_ex(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, int residual_shared,
+                                            wsovod_stream_t stream) {
+  WS_CHECK_ARG(br, "wsovod_gemm_conv_branches_ex: null branch descriptor");
+  return gemm_nt_impl(d, br, stream, &residual_shared);
 }

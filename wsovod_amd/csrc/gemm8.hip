@@ -63,6 +63,9 @@ __device__ __forceinline__ void g8_read_imm(__attribute__((ext_vector_type(4))) 
 #include "gemm8_kernel.h"
 #define WSOVOD_CONV_BRANCHES 1
 #include "gemm8_kernel.h"
+#define WSOVOD_CONV_BRANCHES_EX 1
+#include "gemm8_kernel.h"
+#undef WSOVOD_CONV_BRANCHES_EX
 #undef WSOVOD_CONV_BRANCHES
 
 // split-K finalize: C[m][n] = epilogue(sum over the K slices) -- the epilogue chain of the GEMM kernels, element-wise
@@ -90,18 +93,7 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(const GemmArgs p) 
 
 // The branch-batched bf16x2 conv: ONE launch of the lean two-phase tile over n_branch stacks of row tiles (a.M, a.a_bytes:
 // one branch's).  No split-K: the single-launch summation order of the tile, per branch.
-int launch_gemm256_8ph_branches(const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input,
-                                hipStream_t s, double flops, double bytes) {
-  static int slot = wsovod::prof_slot("conv_igemm_bf16x2_256x256_8ph_branches");
-  static bool attr_set = false;
-  constexpr int lds_bytes = 2 * (256 + 256) * 128;
-  if (!attr_set) {
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_br_kernel<true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                 "wsovod_gemm_conv_branches: LDS opt-in");
-    attr_set = true;
-  }
-  GemmBrArgs args;
-  memset(&args, 0, sizeof(args));
+static void branch_grid(GemmBrArgs& args, const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input) {
   static_cast<GemmArgs&>(args) = a;
   args.tiles_per_branch = ceil_div(a.M, 256);
   args.tiles_m = args.tiles_per_branch * n_branch;
@@ -120,9 +112,46 @@ int launch_gemm256_8ph_branches(const GemmArgs& a, int n_branch, const int* dil,
   }
   args.a_branch_bytes = shared_input ? 0 : a.a_bytes;
   args.c_branch_bytes = (long long)a.M * a.ldc * 4;
+}
+
+int launch_gemm256_8ph_branches(const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input,
+                                hipStream_t s, double flops, double bytes) {
+  static int slot = wsovod::prof_slot("conv_igemm_bf16x2_256x256_8ph_branches");
+  static bool attr_set = false;
+  constexpr int lds_bytes = 2 * (256 + 256) * 128;
+  if (!attr_set) {
+    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_br_kernel<true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
+                 "wsovod_gemm_conv_branches: LDS opt-in");
+    attr_set = true;
+  }
+  GemmBrArgs args;
+  memset(&args, 0, sizeof(args));
+  branch_grid(args, a, n_branch, dil, pad, shared_input);
   wsovod::ProfScope prof(slot, s, flops, bytes);
   hipLaunchKernelGGL((gemm256_8ph_br_kernel<true, true, 2, true>), dim3(args.tiles_m * args.tiles_n), dim3(512), lds_bytes, s, args);
   WS_CHECK_LAUNCH("wsovod_gemm_conv_branches(256x256 8-phase)");
+  return WSOVOD_OK;
+}
+
+// wsovod_gemm_conv_branches_ex: the same grid on gemm256_8ph_brx_kernel, whose prologue also moves the residual pointer to
+// the tile's branch (shared_residual: every branch adds the SAME (M, N) rows, block 0 of an MRRP residual stage)
+int launch_gemm256_8ph_branches_ex(const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input,
+                                   bool shared_residual, hipStream_t s, double flops, double bytes) {
+  static int slot = wsovod::prof_slot("conv_igemm_bf16x2_256x256_8ph_branches_ex");
+  static bool attr_set = false;
+  constexpr int lds_bytes = 2 * (256 + 256) * 128;
+  if (!attr_set) {
+    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_brx_kernel<true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
+                 "wsovod_gemm_conv_branches_ex: LDS opt-in");
+    attr_set = true;
+  }
+  GemmBrExArgs args;
+  memset(&args, 0, sizeof(args));
+  branch_grid(args, a, n_branch, dil, pad, shared_input);
+  args.r_branch_bytes = (!a.residual || shared_residual) ? 0 : (long long)a.M * a.ldr * (a.dtype_r == WSOVOD_BF16 ? 2 : 4);
+  wsovod::ProfScope prof(slot, s, flops, bytes);
+  hipLaunchKernelGGL((gemm256_8ph_brx_kernel<true, true, 2, true>), dim3(args.tiles_m * args.tiles_n), dim3(512), lds_bytes, s, args);
+  WS_CHECK_LAUNCH("wsovod_gemm_conv_branches_ex(256x256 8-phase)");
   return WSOVOD_OK;
 }
 

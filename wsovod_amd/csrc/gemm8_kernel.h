@@ -1,13 +1,19 @@
-// The 8-wavefront 256 x 256 tile kernel of gemm8.hip, which includes this text TWICE: as gemm256_8ph_kernel and, with
-// WSOVOD_CONV_BRANCHES defined, as gemm256_8ph_br_kernel (the branch-batched conv of wsovod_gemm_conv_branches).  A second
-// compilation of the same text instead of a template constant: the first one's code cannot change with the second's.
+// The 8-wavefront 256 x 256 tile kernel of gemm8.hip, which includes this text THREE times: as gemm256_8ph_kernel, with
+// WSOVOD_CONV_BRANCHES defined as gemm256_8ph_br_kernel (the branch-batched conv of wsovod_gemm_conv_branches), and with
+// WSOVOD_CONV_BRANCHES_EX defined next to it as gemm256_8ph_brx_kernel (wsovod_gemm_conv_branches_ex: + the residual's
+// branch offset).  Further compilations of the same text instead of a template constant: the earlier ones' code cannot
+// change with a later one's.
 #if !defined(WSOVOD_CONV_BRANCHES)
 template <bool CONV, bool X3 = false, int PH = 4, bool LEAN = false>
 __global__ __launch_bounds__(512) void gemm256_8ph_kernel(const GemmArgs p) {
   static_assert(!LEAN || PH == 2, "the lean form is a two-phase K-step");
-#else  // the branch-batched conv form (GemmBrArgs): the same text, compiled a second time under another name
+#else  // the branch-batched conv forms (GemmBrArgs / GemmBrExArgs): the same text, compiled again under another name
 template <bool CONV, bool X3 = false, int PH = 4, bool LEAN = false>
+#if defined(WSOVOD_CONV_BRANCHES_EX)
+__global__ __launch_bounds__(512) void gemm256_8ph_brx_kernel(const GemmBrExArgs pa) {
+#else
 __global__ __launch_bounds__(512) void gemm256_8ph_br_kernel(const GemmBrArgs pa) {
+#endif
   static_assert(CONV && LEAN && PH == 2, "branches are a form of the lean conv tile");
   GemmArgs pbr = pa;  // this tile's view of the arguments: see below
   const GemmArgs& p = pbr;
@@ -40,6 +46,11 @@ __global__ __launch_bounds__(512) void gemm256_8ph_br_kernel(const GemmBrArgs pa
   const int br = tile_m / pa.tiles_per_branch;
   pbr.A += (long long)br * pa.a_branch_bytes;
   pbr.C = (char*)pbr.C + (long long)br * pa.c_branch_bytes;
+#if defined(WSOVOD_CONV_BRANCHES_EX)
+  // the branch's rows of the residual (r_branch_bytes 0: ONE map shared by every branch); the epilogue then adds it and
+  // applies the ReLU exactly as the single-dilation tile does
+  if (pbr.residual) pbr.residual = (const char*)pbr.residual + (long long)br * pa.r_branch_bytes;
+#endif
   pbr.dil = br == 0 ? pa.dil[0] : br == 1 ? pa.dil[1] : br == 2 ? pa.dil[2] : pa.dil[3];
   pbr.pad = br == 0 ? pa.pad[0] : br == 1 ? pa.pad[1] : br == 2 ? pa.pad[2] : pa.pad[3];
   const int m0 = (tile_m - br * pa.tiles_per_branch) * BM, n0 = tile_n * BN;

@@ -64,6 +64,11 @@ struct MxBrArgs : MxArgs {
   int dil[4], pad[4];
   long long a_branch_bytes, c_branch_bytes;
 };
+// wsovod_gemm_f16mx_conv_branches_ex: the same with a residual at g.residual + b * r_branch_bytes (0: ONE shared (N, Ho, Wo,
+// Cout) residual added to every branch) and 1x1 filters next to 3x3
+struct MxBrExArgs : MxBrArgs {
+  long long r_branch_bytes;
+};
 
 template <int OFF>
 __device__ __forceinline__ void mx_read(u32x4& dst, unsigned addr) {
@@ -79,6 +84,9 @@ __device__ __forceinline__ i32x8 mx_cat(const u32x4 a, const u32x4 b) {
 #include "gemm8mx_kernel.h"
 #define WSOVOD_CONV_BRANCHES 1
 #include "gemm8mx_kernel.h"
+#define WSOVOD_CONV_BRANCHES_EX 1
+#include "gemm8mx_kernel.h"
+#undef WSOVOD_CONV_BRANCHES_EX
 #undef WSOVOD_CONV_BRANCHES
 
 // split-K finalize: C[m][n] = epilogue(sum over the K slices) for 4 consecutive columns per thread -- the same chain and the
@@ -236,12 +244,38 @@ extern "C" int wsovod_f16mx_from_bf16x2(const void* src, void* dst, long long n,
   return WSOVOD_OK;
 }
 
-// br != NULL: the branch-batched conv of wsovod_gemm_f16mx_conv_branches (d->M, geom.n_img: ONE branch's)
+// br != NULL: the branch-batched conv of wsovod_gemm_f16mx_conv_branches (d->M, geom.n_img: ONE branch's); ex != NULL: its
+// _ex form (residual epilogue, *ex = the residual is ONE map shared by the branches; 1x1 filters next to 3x3)
 static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_scale, int a_segments,
                            const unsigned char* b_scale, int b_segments, void* c_bf16, long long ld_c_bf16,
-                           const wsovod_conv_branches* br, wsovod_stream_t stream) {
+                           const wsovod_conv_branches* br, wsovod_stream_t stream, const int* ex = nullptr) {
   WS_CHECK_ARG(d && b_scale, "wsovod_gemm_f16mx: null descriptor / weight scale array");
-  if (br) {
+  wsovod_gemm_desc d1x1;
+  wsovod_conv_branches br1x1;
+  if (br && ex) {
+    WS_CHECK_ARG(br->n_branch >= 1 && br->n_branch <= 4, "wsovod_gemm_f16mx_conv_branches_ex: n_branch=%d must be 1 - 4", br->n_branch);
+    WS_CHECK_ARG(d->conv && !d->A2 && d->dropout_p == 0.f && !c_bf16 && !a_scale && d->alpha == 1.0f,
+                 "wsovod_gemm_f16mx_conv_branches_ex: a conv with the bias + residual + ReLU epilogue (no shortcut, dropout, bf16 copy)");
+    const bool k3 = d->geom.KH == 3 && d->geom.KW == 3, k1 = d->geom.KH == 1 && d->geom.KW == 1;
+    WS_CHECK_ARG((k3 || k1) && d->geom.stride == 1 && d->geom.Ho == d->geom.H && d->geom.Wo == d->geom.W,
+                 "wsovod_gemm_f16mx_conv_branches_ex: 3x3 or 1x1, stride 1, output of the input's size");
+    WS_CHECK_ARG(!d->residual || d->dtype_r == WSOVOD_F16MX || d->dtype_r == WSOVOD_BF16X2 || d->dtype_r == WSOVOD_F32,
+                 "wsovod_gemm_f16mx_conv_branches_ex: the residual is f16mx, bf16x2 or fp32");
+    WS_CHECK_ARG(d->dtype_c == WSOVOD_F16MX || d->dtype_c == WSOVOD_BF16X2 || d->dtype_c == WSOVOD_F32,
+                 "wsovod_gemm_f16mx_conv_branches_ex: the output is f16mx, bf16x2 or fp32");
+    if (k1) {  // a 1x1 filter has no dilation: every branch runs it at dil 1 / pad 0 on its own rows
+      d1x1 = *d;
+      br1x1 = *br;
+      d1x1.geom.dil = 1;
+      d1x1.geom.pad = 0;
+      for (int b = 0; b < 4; ++b) br1x1.dil[b] = 1, br1x1.pad[b] = 0;
+      d = &d1x1;
+      br = &br1x1;
+    } else {
+      for (int b = 0; b < br->n_branch; ++b)
+        WS_CHECK_ARG(br->dil[b] >= 1 && br->pad[b] == br->dil[b], "wsovod_gemm_f16mx_conv_branches_ex: branch %d needs pad == dil >= 1", b);
+    }
+  } else if (br) {
     WS_CHECK_ARG(br->n_branch >= 1 && br->n_branch <= 4, "wsovod_gemm_f16mx_conv_branches: n_branch=%d must be 1 - 4", br->n_branch);
     WS_CHECK_ARG(d->conv && !d->A2 && !d->residual && d->dropout_p == 0.f && !c_bf16 && !a_scale,
                  "wsovod_gemm_f16mx_conv_branches: a conv with the bias + ReLU epilogue (no shortcut, residual, dropout, bf16 copy)");
@@ -377,6 +411,11 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
                  "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
     WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_mx_br_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
                  "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
+#define MX_OPT_IN_X(E)                                                                                                       \
+  WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_mx_brx_kernel<true, E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), \
+               "wsovod_gemm_f16mx_conv_branches_ex: LDS opt-in")
+    MX_OPT_IN_X(0); MX_OPT_IN_X(1); MX_OPT_IN_X(2); MX_OPT_IN_X(3);
+#undef MX_OPT_IN_X
     attr_set = true;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -440,7 +479,33 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
     }
   }
   static int slot_b = wsovod::prof_slot("conv_igemm_f16mx_256x256_8ph_branches");
-  wsovod::ProfScope prof(br ? slot_b : d->conv ? slot_c : slot_g, s, 2.0 * d->M * nbr * (double)d->N * d->K, bytes);
+  static int slot_bx = wsovod::prof_slot("conv_igemm_f16mx_256x256_8ph_branches_ex");
+  wsovod::ProfScope prof(br ? (ex ? slot_bx : slot_b) : d->conv ? slot_c : slot_g, s, 2.0 * d->M * nbr * (double)d->N * d->K, bytes);
+  if (br && ex) {
+    MxBrExArgs qb;
+    memset(&qb, 0, sizeof(qb));
+    static_cast<MxArgs&>(qb) = q;
+    qb.tiles_per_branch = (d->M + 255) / 256;
+    for (int b = 0; b < 4; ++b) {
+      qb.dil[b] = br->dil[b < nbr ? b : 0];
+      qb.pad[b] = br->pad[b < nbr ? b : 0];
+    }
+    qb.a_branch_bytes = br->shared_input ? 0 : a.a_bytes;
+    qb.c_branch_bytes = (long long)d->M * d->ldc * 4;
+    qb.r_branch_bytes = (!d->residual || *ex) ? 0 : (long long)d->M * d->ldr * (d->dtype_r == WSOVOD_BF16 ? 2 : 4);
+    // (EPI exactly as the single-dilation conv entry chooses it below: the same build of the epilogue, the same bits)
+    const bool mxr = d->residual && d->dtype_r == WSOVOD_F16MX;
+    const int epi = d->N % 64 != 0 ? 0 : (d->dtype_c == WSOVOD_F16MX && !d->residual) ? 1 : (d->dtype_c == WSOVOD_F16MX && mxr) ? 2
+                    : (d->dtype_c == WSOVOD_F32 && mxr) ? 3 : 0;
+#define MX_LAUNCH_X(E) hipLaunchKernelGGL((gemm256_mx_brx_kernel<true, E>), dim3(ntiles), dim3(512), lds_bytes, s, qb)
+    if (epi == 1) MX_LAUNCH_X(1);
+    else if (epi == 2) MX_LAUNCH_X(2);
+    else if (epi == 3) MX_LAUNCH_X(3);
+    else MX_LAUNCH_X(0);
+#undef MX_LAUNCH_X
+    WS_CHECK_LAUNCH("wsovod_gemm_f16mx_conv_branches_ex");
+    return WSOVOD_OK;
+  }
   if (br) {
     MxBrArgs qb;
     memset(&qb, 0, sizeof(qb));
@@ -519,4 +584,10 @@ extern "C" int wsovod_gemm_f16mx_conv_branches(const wsovod_gemm_desc* d, const 
                                                const unsigned char* b_scale, int b_segments, wsovod_stream_t stream) {
   WS_CHECK_ARG(br, "wsovod_gemm_f16mx_conv_branches: null branch descriptor");
   return gemm_f16mx_impl(d, nullptr, 1, b_scale, b_segments, nullptr, 0, br, stream);
+}
+
+extern "C" int wsovod_gemm_f16mx_conv_branches_ex(const wsovod_gemm_desc* d, const wsovod_conv_branches* br, int residual_shared,
+                                                  const unsigned char* b_scale, int b_segments, wsovod_stream_t stream) {
+  WS_CHECK_ARG(br, "wsovod_gemm_f16mx_conv_branches_ex: null branch descriptor");
+  return gemm_f16mx_impl(d, nullptr, 1, b_scale, b_segments, nullptr, 0, br, stream, &residual_shared);
 }

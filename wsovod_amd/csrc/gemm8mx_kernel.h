@@ -1,6 +1,8 @@
-// The 256 x 256 f16mx tile kernel of gemm8mx.hip, which includes this text TWICE: as gemm256_mx_kernel and, with
-// WSOVOD_CONV_BRANCHES defined, as gemm256_mx_br_kernel (the branch-batched conv of wsovod_gemm_f16mx_conv_branches).  A
-// second compilation of the same text instead of a template constant: the first one's code cannot change with the second's.
+// The 256 x 256 f16mx tile kernel of gemm8mx.hip, which includes this text THREE times: as gemm256_mx_kernel, with
+// WSOVOD_CONV_BRANCHES defined as gemm256_mx_br_kernel (the branch-batched conv of wsovod_gemm_f16mx_conv_branches), and with
+// WSOVOD_CONV_BRANCHES_EX defined next to it as gemm256_mx_brx_kernel (wsovod_gemm_f16mx_conv_branches_ex: + the residual's
+// branch offset).  Further compilations of the same text instead of a template constant: the earlier ones' code cannot change
+// with a later one's.
 // EPI: the epilogue's output / residual formats as compile-time facts (0 = read from the arguments: every combination, ~100 KB
 // of code behind runtime branches that each tile streamed through the instruction cache; the hot combinations are built
 // apart): 1 = f16mx out, no residual; 2 = f16mx out + f16mx residual; 3 = fp32 out + f16mx residual; 4 = bf16x2 out, no
@@ -9,9 +11,13 @@
 template <bool CONV, int EPI = 0>
 __global__ __launch_bounds__(512) void gemm256_mx_kernel(const MxArgs q) {
   const GemmArgs& p = q.g;
-#else  // the branch-batched conv form (MxBrArgs): the same text, compiled a second time under another name
+#else  // the branch-batched conv forms (MxBrArgs / MxBrExArgs): the same text, compiled again under another name
 template <bool CONV, int EPI = 0>
+#if defined(WSOVOD_CONV_BRANCHES_EX)
+__global__ __launch_bounds__(512) void gemm256_mx_brx_kernel(const MxBrExArgs q) {
+#else
 __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
+#endif
   static_assert(CONV, "branches are a conv form");
   GemmArgs pbr = q.g;  // this tile's view of the arguments: see below
   const GemmArgs& p = pbr;
@@ -43,6 +49,11 @@ __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
   const int br = tile_m / q.tiles_per_branch;
   pbr.A += (long long)br * q.a_branch_bytes;
   pbr.C = (char*)pbr.C + (long long)br * q.c_branch_bytes;
+#if defined(WSOVOD_CONV_BRANCHES_EX)
+  // the branch's rows of the residual (r_branch_bytes 0: ONE map shared by every branch); the epilogue then adds it and
+  // applies the ReLU exactly as the single-dilation tile does
+  if (pbr.residual) pbr.residual = (const char*)pbr.residual + (long long)br * q.r_branch_bytes;
+#endif
   pbr.dil = br == 0 ? q.dil[0] : br == 1 ? q.dil[1] : br == 2 ? q.dil[2] : q.dil[3];
   pbr.pad = br == 0 ? q.pad[0] : br == 1 ? q.pad[1] : br == 2 ? q.pad[2] : q.pad[3];
   [[maybe_unused]] const int m0 = (tile_m - br * q.tiles_per_branch) * BM, n0 = tile_n * BN;

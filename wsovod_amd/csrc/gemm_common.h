@@ -61,6 +61,11 @@ struct GemmBrArgs : GemmArgs {
   int dil[4], pad[4];
   long long a_branch_bytes, c_branch_bytes;
 };
+// wsovod_gemm_conv_branches_ex: the same with a residual (d->residual) at residual + b * r_branch_bytes (0: ONE shared
+// (N, Ho, Wo, Cout) residual added to every branch) and 1x1 filters next to 3x3
+struct GemmBrExArgs : GemmBrArgs {
+  long long r_branch_bytes;
+};
 
 template <typename T>
 struct Traits;
@@ -191,5 +196,8 @@ int launch_gemm256_8ph(const GemmArgs& a, bool conv, hipStream_t s, double flops
 // the lean two-phase bf16x2 conv tile over n_branch dilations in ONE launch (a.M, a.a_bytes: one branch's)
 int launch_gemm256_8ph_branches(const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input,
                                 hipStream_t s, double flops, double bytes);
+// the same with the residual epilogue (a.residual: one branch's rows, or with shared_residual ONE map for every branch)
+int launch_gemm256_8ph_branches_ex(const GemmArgs& a, int n_branch, const int* dil, const int* pad, bool shared_input,
+                                   bool shared_residual, hipStream_t s, double flops, double bytes);
 
 }  // namespace wsovod_gemm

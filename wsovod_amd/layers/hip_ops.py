@@ -576,9 +576,13 @@ def gemm_mx(A, a_scale, B, b_scale, *, bias=None, relu=False, dropout_p=0.0, dro
     return carrier.tag(out, out_dtype, out_bf16 if out_dtype == MX else None) if out_dtype in (X2, MX) else out
 
 
-def conv_branches(A, B, geom, dilations, *, shared_input, b_scale=None, bias=None, relu=False, out_dtype=None, out=None):
+def conv_branches(A, B, geom, dilations, *, shared_input, b_scale=None, bias=None, relu=False, out_dtype=None, out=None,
+                  residual=None, residual_shared=False, residual_fmt=None):
     """The same 3x3 / stride-1 filter at up to four dilations in ONE launch (wsovod_gemm_conv_branches, or with b_scale its
-    f16mx twin wsovod_gemm_f16mx_conv_branches).  A: the NHWC bf16x2 / unit-scale f16mx input -- ONE (N, H, W, Cin) map
+    f16mx twin wsovod_gemm_f16mx_conv_branches).  With a residual, or a 1x1 filter (geom KH = KW = 1: the dilations only count
+    the branches), the `_ex` entries: residual is added ahead of the ReLU -- (len(dilations) * N * H * W, Cout) branch-major
+    rows, or with residual_shared ONE (N * H * W, Cout) map added to every branch -- in residual_fmt (default: the operands'
+    carrier format; float32 for a plain fp32 tensor).  A: the NHWC bf16x2 / unit-scale f16mx input -- ONE (N, H, W, Cin) map
     with shared_input, else (len(dilations) * N, H, W, Cin) branch-major; B: the encoded (Cout, 9 Cin) weight; geom: the
     geometry dict of gemm_nt with n_img = the per-branch N.  Returns the (len(dilations) * N * H * W, Cout) branch-major
     output in out_dtype (X2, MX -- f16mx operands only -- or float32): torch.cat of the per-dilation convs.  out: an optional
@@ -596,7 +600,8 @@ def conv_branches(A, B, geom, dilations, *, shared_input, b_scale=None, bias=Non
     d.N, d.K = B.size(0), B.size(1)
     d.B, d.ldb = B.data_ptr(), _ld(B)
     g = _set_conv(d, A, geom)
-    g.dil = g.pad = int(dilations[0])
+    k1 = g.KH == 1 and g.KW == 1
+    g.dil, g.pad = (1, 0) if k1 else (int(dilations[0]),) * 2
     if A.numel() != (1 if shared_input else nb) * g.n_img * g.H * g.W * g.Cin:
         raise RuntimeError("wsovod_hip conv_branches: the input is (N, H, W, Cin) when shared, else (n_branch * N, H, W, Cin)")
     out_dtype = out_dtype or (MX if mx else X2)
@@ -619,7 +624,23 @@ def conv_branches(A, B, geom, dilations, *, shared_input, b_scale=None, bias=Non
     br.n_branch, br.shared_input = nb, int(bool(shared_input))
     for b, dl in enumerate(dilations):
         br.dil[b] = br.pad[b] = int(dl)
-    if mx:
+    if residual is not None or k1:
+        if residual is not None:
+            require_gpu(residual)
+            residual_fmt = residual_fmt or (MX if mx else X2)
+            if residual.dtype != torch.float32 or residual.dim() != 2 or residual.size(1) != d.N \
+                    or residual.size(0) != (1 if residual_shared else nb) * d.M or (residual_fmt == MX and not mx):
+                raise RuntimeError("wsovod_hip conv_branches: the residual is (N * H * W, Cout) when shared, else (n_branch * N * "
+                                   "H * W, Cout), float32-typed (an f16mx one needs f16mx operands)")
+            d.residual, d.ldr, d.dtype_r = residual.data_ptr(), _ld(residual), fmt_code(residual_fmt)
+        if mx:
+            assert b_scale.dtype == torch.uint8 and b_scale.is_contiguous()
+            check(lib().wsovod_gemm_f16mx_conv_branches_ex(C.byref(d), C.byref(br), int(bool(residual_shared)), ptr(b_scale),
+                                                           int(b_scale.shape[1]), stream()), "gemm_f16mx_conv_branches_ex")
+        else:
+            check(lib().wsovod_gemm_conv_branches_ex(C.byref(d), C.byref(br), int(bool(residual_shared)), stream()),
+                  "gemm_conv_branches_ex")
+    elif mx:
         assert b_scale.dtype == torch.uint8 and b_scale.is_contiguous()
         check(lib().wsovod_gemm_f16mx_conv_branches(C.byref(d), C.byref(br), ptr(b_scale), int(b_scale.shape[1]), stream()),
               "gemm_f16mx_conv_branches")

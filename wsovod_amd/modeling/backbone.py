@@ -494,13 +494,11 @@ def make_stage(*args, **kwargs):
     return ResNet.make_stage(*args, **kwargs)
 
 
-@BACKBONE_REGISTRY.register()
-def build_wsl_resnet_backbone(cfg, input_shape):
-    """resnet_wsl.py:623-707 (stage wiring: stride-by-maxpool, dilated res4/res5)."""
+def wsl_resnet_stem_and_stages(cfg, input_shape, stage_hook=None):
+    """resnet_wsl.py:623-707 (stage wiring: stride-by-maxpool, dilated res4/res5) -> (stem, [blocks of res2 .. res5]).
+    stage_hook(stage_idx, stage_kargs): may rewrite the `make_stage` arguments of a stage (backbone_resnet_mrrp.py)."""
     norm = cfg.MODEL.RESNETS.NORM
     stem = BasicStem(in_channels=input_shape.channels, out_channels=cfg.MODEL.RESNETS.STEM_OUT_CHANNELS, norm=norm)
-    freeze_at = cfg.MODEL.BACKBONE.FREEZE_AT
-    out_features = cfg.MODEL.RESNETS.OUT_FEATURES
     depth = cfg.MODEL.RESNETS.DEPTH
     num_groups = cfg.MODEL.RESNETS.NUM_GROUPS
     width_per_group = cfg.MODEL.RESNETS.WIDTH_PER_GROUP
@@ -531,9 +529,18 @@ def build_wsl_resnet_backbone(cfg, input_shape):
         else:
             stage_kargs.update(block_class=BottleneckBlock, bottleneck_channels=bottleneck_channels,
                                stride_in_1x1=stride_in_1x1, num_groups=num_groups)
+        if stage_hook is not None:
+            stage_hook(stage_idx, stage_kargs)
         stages.append(ResNet.make_stage(**stage_kargs))
         in_channels = out_channels
         out_channels *= 2
         bottleneck_channels *= 2
-    return ResNet(stem, stages, out_features=out_features, freeze_at=freeze_at,
+    return stem, stages
+
+
+@BACKBONE_REGISTRY.register()
+def build_wsl_resnet_backbone(cfg, input_shape):
+    """resnet_wsl.py:623-707."""
+    stem, stages = wsl_resnet_stem_and_stages(cfg, input_shape)
+    return ResNet(stem, stages, out_features=cfg.MODEL.RESNETS.OUT_FEATURES, freeze_at=cfg.MODEL.BACKBONE.FREEZE_AT,
                   precision=forward_precision(cfg.MODEL.HIP.PRECISION))

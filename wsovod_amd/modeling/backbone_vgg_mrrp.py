@@ -52,19 +52,26 @@ def _batched_images(conv, Hh, Ww, dilations):
     return (C.CONV_MAX_OPERAND_BYTES - (pmax * Ww + pmax) * conv.in_channels * 4) // per_image
 
 
-def hip_conv_branches(x, conv, dilations, shared_input, relu=False, out_fp32=False, batched=None):
+def hip_conv_branches(x, conv, dilations, shared_input, relu=False, out_fp32=False, batched=None, residual=None,
+                      residual_shared=False):
     """`conv` (3x3, stride 1) at every dilation of `dilations` with padding = dilation.  x: with shared_input ONE (N, H, W,
     Cin) NHWC map read by every branch (MRRPPlainBlock.conv1, where x = [x] * num_branch), else (len(dilations) * N, H, W,
     Cin), branch-major.  Returns (len(dilations) * N, H, W, Cout), branch-major: torch.cat([conv(x_b, dilation=d_b)]).
-    batched: True / False forces the one-launch form / the loop (None: branch_batched_default)."""
+    batched: True / False forces the one-launch form / the loop (None: branch_batched_default).
+    residual: a map in x's format added ahead of the ReLU, as `hip_conv`'s -- (len(dilations) * N, H, W, Cout) branch-major,
+    or with residual_shared ONE (N, H, W, Cout) map added to every branch (block 0 of an MRRP residual stage, whose
+    projection shortcut is the same for every branch: backbone_resnet_mrrp.py).  A 1x1 / stride-1 / unpadded `conv` is taken
+    too (the dilations then only count the branches): the Bottleneck's tail conv over the branches with that shared residual."""
     nb = len(dilations)
     if not 1 <= nb <= MAX_BRANCHES:
         raise NotImplementedError(f"wsovod_amd: {nb} MRRP branches (MODEL.MRRP.NUM_BRANCH): at most {MAX_BRANCHES} are built")
-    if conv.kernel_size != 3 or conv.stride != 1:
-        raise NotImplementedError("wsovod_amd: MRRP branches share a 3x3 / stride-1 conv")
+    k1 = conv.kernel_size == 1 and conv.padding == 0
+    if (conv.kernel_size != 3 and not k1) or conv.stride != 1:
+        raise NotImplementedError("wsovod_amd: MRRP branches share a 3x3 / stride-1 conv (or a 1x1 / stride-1 one)")
     NB, Hh, Ww, Cin = x.shape
     N = NB if shared_input else NB // nb
     assert shared_input or NB == nb * N
+    assert residual is None or residual.shape == ((N if residual_shared else nb * N), Hh, Ww, conv.out_channels)
     if batched is None:
         batched = H.x2_active() and conv.in_channels % 32 == 0 and conv.out_channels % 32 == 0 \
             and branch_batched_default(H.mx_of(x), N)
@@ -84,14 +91,20 @@ def hip_conv_branches(x, conv, dilations, shared_input, relu=False, out_fp32=Fal
                 j = min(N, i + max_n)
                 xb = part(x, i, j) if shared_input else \
                     carrier.like(x, torch.cat([x[bi * N + i:bi * N + j] for bi in range(nb)]))
-                outs.append((j - i, hip_conv_branches(xb, conv, dilations, shared_input, relu=relu, out_fp32=out_fp32, batched=True)))
+                rb = None if residual is None else part(residual, i, j) if residual_shared else \
+                    carrier.like(residual, torch.cat([residual[bi * N + i:bi * N + j] for bi in range(nb)]))
+                outs.append((j - i, hip_conv_branches(xb, conv, dilations, shared_input, relu=relu, out_fp32=out_fp32, batched=True,
+                                                      residual=rb, residual_shared=residual_shared)))
             return carrier.like(outs[0][1], torch.cat([o[bi * n:(bi + 1) * n] for bi in range(nb) for n, o in outs]))
-        geom = dict(n_img=N, H=Hh, W=Ww, Cin=Cin, Ho=Hh, Wo=Ww, KH=3, KW=3, stride=1, pad=dilations[0], dil=dilations[0])
+        k = conv.kernel_size
+        geom = dict(n_img=N, H=Hh, W=Ww, Cin=Cin, Ho=Hh, Wo=Ww, KH=k, KW=k, stride=1, pad=dilations[0], dil=dilations[0])
         fmt = H.MX if H.mx_of(x) else H.X2
         out_fmt = torch.float32 if out_fp32 else fmt
         w, w_scale, b = conv_operand(conv, fmt, cin_pad=Cin)
+        assert residual is None or bool(H.mx_of(residual)) == (fmt == H.MX)
         out = H.conv_branches(x, w, geom, dilations, shared_input=shared_input, b_scale=w_scale, bias=b, relu=relu,
-                              out_dtype=out_fmt)
+                              out_dtype=out_fmt, residual=None if residual is None else residual.view(-1, conv.out_channels),
+                              residual_shared=residual_shared, residual_fmt=fmt)
         if out_fmt == H.MX:
             mx_guard.audit(conv, out)
         return out.view(nb * N, Hh, Ww, conv.out_channels)  # (a whole view of what conv_branches tagged)
@@ -100,7 +113,8 @@ def hip_conv_branches(x, conv, dilations, shared_input, relu=False, out_fp32=Fal
     parts = []
     for bi, d in enumerate(dilations):
         xb = x if shared_input else carrier.like(x, x[bi * N:(bi + 1) * N])
-        parts.append(hip_conv(xb, conv, relu=relu, out_fp32=out_fp32, dilation=int(d)))
+        rb = residual if residual is None or residual_shared else carrier.like(residual, residual[bi * N:(bi + 1) * N])
+        parts.append(hip_conv(xb, conv, relu=relu, residual=rb, out_fp32=out_fp32, dilation=None if k1 else int(d)))
     return parts[0] if nb == 1 else carrier.like(parts[0], torch.cat(parts))
 
 

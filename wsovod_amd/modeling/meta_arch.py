@@ -85,7 +85,8 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         stacked, branches = getattr(backbone, "mrrp_stacked", False), getattr(backbone, "mrrp_num_branch", 1)
         if cfg.MODEL.MRRP.MRRP_ON and not stacked:
             raise NotImplementedError(f"MODEL.MRRP.MRRP_ON with {cfg.MODEL.BACKBONE.NAME}: the heads expect an MRRP backbone's "
-                                      "branch-major map (built: build_mrrp_vgg_backbone with plain5 in MRRP_STAGE)")
+                                      "branch-major map (built: build_mrrp_vgg_backbone with plain5 in MRRP_STAGE, "
+                                      "build_mrrp_wsl_resnet_backbone with MRRP_STAGE res5)")
         if not cfg.MODEL.MRRP.MRRP_ON and stacked:
             raise NotImplementedError(f"{cfg.MODEL.BACKBONE.NAME} stacks {branches} MRRP branches along N but MODEL.MRRP.MRRP_ON is "
                                       "False: the heads would pool every box from branch 0")

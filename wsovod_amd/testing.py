@@ -17,11 +17,13 @@ def hot_path_cfg(depth=18, K=20, D=512, precision="bf16", pooler="ROIPool", devi
     /root/reference/configs/PascalVOC-Detection/{Base-RCNN-DilatedC5,WSOVOD_WSR_18_DC5_1x}.yaml
     that the hot path reads, with PROPOSAL_GENERATOR=PrecomputedProposals, BBOX_REFINE off.
     backbone="vgg16": WSOVOD_V_16_DC5_1x instead (hot_path_vgg16.yaml; `depth` is not read); with mrrp its MRRP form
-    (hot_path_vgg16_mrrp.yaml: precomputed proposals only)."""
+    (hot_path_vgg16_mrrp.yaml: precomputed proposals only).  backbone="resnet" with mrrp: WSOVOD_MRRP_WSR_{18,50}_DC5_1x
+    (hot_path_r{18,50}_mrrp.yaml: precomputed proposals only)."""
     cfg = get_cfg()
     if mrrp:
-        assert backbone == "vgg16" and not rpn, "the MRRP hot path is the VGG16 one with precomputed proposals"
-        cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_mrrp.yaml"))
+        assert backbone in ("vgg16", "resnet") and not rpn, "the MRRP hot paths run with precomputed proposals"
+        name = "hot_path_vgg16_mrrp.yaml" if backbone == "vgg16" else f"hot_path_r{depth}_mrrp.yaml"
+        cfg.merge_from_file(os.path.join(_CONFIG_DIR, name))
     elif backbone == "vgg16":
         cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_rpn.yaml" if rpn else "hot_path_vgg16.yaml"))
     else:

@@ -580,6 +580,33 @@ int wsovod_rpn_decode(const float* anchors, const float* deltas, const long long
                       long long anchors_per_image, const float* image_sizes, const float* weights, float scale_clamp,
                       float min_size, float* boxes, unsigned char* valid, wsovod_stream_t stream);
 
+/* Grouped pre-NMS top-k of the MRRP RPN.  Replaces the per-level, per-anchor-id sort of find_top_rpn_proposals_group
+ * (proposal_utils.py:199-239; levels = the MRRP branches of rpn.py:398-400, stacked along the rows here).
+ *   logits (B, HW, A) f32 contiguous: row b = level * num_images + image of the RPN head's output.
+ * For every (b, a): the k = min(HW, pre_nms_topk) largest of logits[b, :, a], by score descending and position ascending
+ * among equal scores, with torch.sort's order and equality (-0.0 == +0.0; every NaN equals every NaN and ranks above
+ * +inf): bit for bit torch.sort(logits.permute(0, 2, 1), -1, descending=True, stable=True) truncated to k.
+ *   scores (B, A, k) f32: the values themselves; index (B, A, k) int64: the flat position p * A + a (what
+ *   wsovod_rpn_decode indexes anchors and deltas with).
+ * pre_nms_topk > 2048 is refused (WSOVOD_ERR_UNSUPPORTED): one workgroup sorts the selected pairs in LDS. */
+int wsovod_rpn_group_topk(const float* logits, int B, int HW, int A, int pre_nms_topk, float* scores, long long* index,
+                          wsovod_stream_t stream);
+
+/* Merge of the per-group NMS survivors of an image.  Replaces the tail of find_top_rpn_proposals_group
+ * (proposal_utils.py:335-351: batched_nms over idxs = level * 1000 + anchor returns the kept boxes of all groups by
+ * descending score; keep[:post_nms_topk]; level_ids of the kept).
+ *   boxes (num_images*G*seg_len, 4) f32 and scores (num_images*G*seg_len) f32: segment (n, g) owns rows
+ *   [(n*G + g) * seg_len, ... + seg_len); keep_idx / keep_count: what wsovod_nms_segments wrote for those
+ *   num_images*G equal-length segments (no host read in between); G = levels * A, g = level * A + anchor.
+ * Per image: the first post_nms_topk kept boxes by score descending, (group, rank in the group) ascending among
+ * equal scores.  Kept scores are finite (the valid mask excluded the rest).
+ *   out_boxes (num_images, post_nms_topk, 4); out_scores (num_images, post_nms_topk);
+ *   out_level_ids (num_images, post_nms_topk) int64 = (g / A) * 1000 + g % A;
+ *   out_count (num_images) int32 = min(post_nms_topk, sum of the image's keep_count); rows past it are not written. */
+int wsovod_nms_merge_groups(const float* boxes, const float* scores, const int* keep_idx, const int* keep_count,
+                            int num_images, int G, int A, int seg_len, int post_nms_topk, float* out_boxes,
+                            float* out_scores, long long* out_level_ids, int* out_count, wsovod_stream_t stream);
+
 /* RPN anchor labelling: detectron2 pairwise_iou + Matcher(thresholds [lo, hi], labels [0, -1, 1],
  * allow_low_quality_matches=True) (un-vendored) as used by
  * WSOVODRPN_V2.label_and_sample_anchors (rpn.py:237-293) before the random sub-sampling.

@@ -141,6 +141,8 @@ SIGNATURES = {
     "wsovod_rpn_label_anchors": [_P, _I, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P],
     "wsovod_im2col_rows": [_P, _I, _P, _I] + [_I] * 10 + [_P, _P],
     "wsovod_rpn_decode": [_P, _P, _P, _I, _I, _L, _P, C.POINTER(C.c_float), _F, _F, _P, _P, _P],
+    "wsovod_rpn_group_topk": [_P, _I, _I, _I, _I, _P, _P, _P],
+    "wsovod_nms_merge_groups": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 class SgdTensor(C.Structure):

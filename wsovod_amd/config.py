@@ -247,6 +247,9 @@ def add_wsovod_config(cfg):
     # "off" | "warn" | "raise" | "fallback" (to the bf16x2 kernels of "parity"); in training every PERIOD-th step is audited
     _C.MODEL.HIP.MX_RANGE_GUARD = "off"
     _C.MODEL.HIP.MX_RANGE_GUARD_PERIOD = 100
+    # build WSOVODRPN_V2 with MODEL.MRRP.MRRP_ON (per-level anchors, grouped top-k, level ids).  Off by
+    # default only because configs without the key are pinned to the earlier refusal
+    _C.MODEL.HIP.MRRP_RPN = False
     return _C
 
 

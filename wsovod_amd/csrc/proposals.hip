@@ -241,9 +241,239 @@ __global__ __launch_bounds__(256) void rpn_label_kernel(const float4* __restrict
   labels[(long long)b * A + a] = lab;
 }
 
+// ---- grouped top-k of the MRRP RPN (proposal_utils.py:199-239: per level and per anchor id, sort the H*W logits of
+// that anchor and keep min(H*W, pre_nms_topk)) ------------------------------------------------------------------------
+// One workgroup per (row b, anchor a); the row is the HW values logits[b][p][a], stride A.  Order and equality are
+// torch.sort's (descending, stable): every NaN is one value above +inf, -0.0 == +0.0, equal values by position ascending.
+//   1. radix select of the k-th largest over order-preserving 32-bit keys, four 8-bit digits from the top; every wavefront
+//      owns one contiguous quarter of the row and its own LDS histogram, the row is re-read (L2) on each pass
+//   2. compaction into LDS: every key above the threshold, plus the first `ties` keys equal to it by position (the
+//      per-wavefront counts of the last histogram give each quarter its base, so the walk needs no barrier)
+//   3. bitonic sort of the <= 2048 (key, ~position) words in LDS, then coalesced stores of score and flat index p * A + a
+constexpr int kTopkMax = 2048;
+
+__device__ __forceinline__ unsigned int topk_key(float x) {
+  if (x != x) return 0xffffffffu;          // every NaN: one value, above +inf
+  if (x == 0.f) return 0x80000000u;        // -0.0 == +0.0
+  const unsigned int u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void rpn_group_topk_kernel(const float* __restrict__ logits, int HW, int A, int k,
+                                                             float* __restrict__ out_scores,
+                                                             long long* __restrict__ out_index) {
+  __shared__ unsigned long long items[kTopkMax];  // (key << 32) | ~position: descending = key desc, position asc
+  __shared__ unsigned int hist[4][256];
+  __shared__ unsigned int sel[2];                 // digit chosen by the current pass, what remains of k below it
+  __shared__ unsigned int wave_eq[4];             // keys equal to the threshold in each wavefront's quarter
+  __shared__ unsigned int n_above;                // compaction cursor of the keys above the threshold
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x / A, a = blockIdx.x - b * A;
+  const float* row = logits + ((long long)b * HW) * A + a;
+  const int Q = ceil_div(ceil_div(HW, 4), 64) * 64;
+  const int p_begin = min(HW, wave * Q), p_end = min(HW, p_begin + Q);
+
+  unsigned int prefix = 0u, pmask = 0u, rem = (unsigned int)k;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    for (int i = tid; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    for (int p0 = p_begin; p0 < p_end; p0 += 64) {
+      const int p = p0 + lane;
+      if (p < p_end) {
+        const unsigned int key = topk_key(row[(long long)p * A]);
+        if ((key & pmask) == prefix) atomicAdd(&hist[wave][(key >> shift) & 255u], 1u);
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {  // lane l owns the digits 255 - 4l .. 252 - 4l: counts above each digit by a 64-lane scan
+      unsigned int c[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int d = 255 - (4 * lane + j);
+        c[j] = hist[0][d] + hist[1][d] + hist[2][d] + hist[3][d];
+      }
+      const unsigned int mine = c[0] + c[1] + c[2] + c[3];
+      unsigned int incl = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      unsigned int above = incl - mine;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (above < rem && rem <= above + c[j]) {  // exactly one (lane, j): 1 <= rem <= the pass's total
+          sel[0] = 255u - (unsigned int)(4 * lane + j);
+          sel[1] = rem - above;
+        }
+        above += c[j];
+      }
+    }
+    __syncthreads();
+    const unsigned int d = sel[0];
+    rem = sel[1];
+    prefix |= d << shift;
+    pmask |= 255u << shift;
+    if (pass == 3 && tid < 4) wave_eq[tid] = hist[tid][d];
+    if (pass == 3 && tid == 0) n_above = 0u;
+    __syncthreads();
+  }
+  // prefix = the k-th largest key; rem = how many keys equal to it belong to the result (the first by position)
+  const unsigned int thr = prefix, ties = rem, above_total = (unsigned int)k - ties;
+  unsigned int eq_seen = 0u;
+  for (int w = 0; w < wave; ++w) eq_seen += wave_eq[w];
+  int n_sort = 1;
+  while (n_sort < k) n_sort <<= 1;
+  for (int i = k + tid; i < n_sort; i += 256) items[i] = 0ull;  // padding: below every real key, after every position
+  for (int p0 = p_begin; p0 < p_end; p0 += 64) {
+    const int p = p0 + lane;
+    const unsigned int key = p < p_end ? topk_key(row[(long long)p * A]) : 0u;
+    const bool gt = p < p_end && key > thr, eq = p < p_end && key == thr;
+    const unsigned long long m_gt = __ballot(gt), m_eq = __ballot(eq);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned int base = 0u;
+    if (lane == 0 && m_gt) base = atomicAdd(&n_above, (unsigned int)__popcll(m_gt));
+    base = __shfl(base, 0, 64);
+    unsigned int slot = 0xffffffffu;
+    if (gt) slot = base + (unsigned int)__popcll(m_gt & below);
+    if (eq) {
+      const unsigned int r = eq_seen + (unsigned int)__popcll(m_eq & below);
+      if (r < ties) slot = above_total + r;
+    }
+    if (slot < (unsigned int)k) items[slot] = ((unsigned long long)key << 32) | (unsigned int)~(unsigned int)p;
+    eq_seen += (unsigned int)__popcll(m_eq);
+  }
+  for (int size = 2; size <= n_sort; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < (n_sort >> 1); i += 256) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const unsigned long long x = items[lo], y = items[hi];
+        const bool desc = (lo & size) == 0;
+        if (desc ? x < y : x > y) { items[lo] = y; items[hi] = x; }
+      }
+    }
+  }
+  __syncthreads();
+  const long long out0 = (long long)blockIdx.x * k;
+  for (int t = tid; t < k; t += 256) {
+    const unsigned int p = ~(unsigned int)(items[t] & 0xffffffffull);
+    out_scores[out0 + t] = row[(long long)p * A];  // the value itself: the key folds -0.0 and the NaN payloads
+    out_index[out0 + t] = (long long)p * A + a;
+  }
+}
+
+// ---- k-way merge of the per-(level, anchor) NMS survivors (proposal_utils.py:335-351: batched_nms returns the kept boxes
+// of all groups sorted by score, of which the first post_nms_topk are kept) -------------------------------------------
+// One workgroup per image.  List g of the image = the keep_count[n*G+g] positions keep_idx[(n*G+g)*k ...] that
+// wsovod_nms_segments wrote, already by descending score.  The kept scores are staged in LDS; every kept element then
+// counts, list by list with a binary search, the elements ahead of it (equal scores: lower group first), which is its
+// place in the output.  Places are a permutation, so every output row below `count` is written exactly once.
+__global__ __launch_bounds__(1024) void nms_merge_groups_kernel(const float4* __restrict__ boxes,
+                                                                const float* __restrict__ scores,
+                                                                const int* __restrict__ keep_idx,
+                                                                const int* __restrict__ keep_count, int G, int A, int k,
+                                                                int cap, int post, float4* __restrict__ out_boxes,
+                                                                float* __restrict__ out_scores,
+                                                                long long* __restrict__ out_ids,
+                                                                int* __restrict__ out_count) {
+  extern __shared__ float kept[];  // [G][cap], cap = min(post, k): the longest list
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const long long seg0 = (long long)n * G;
+  int total = 0;
+  for (int g = 0; g < G; ++g) total += min(cap, max(0, keep_count[seg0 + g]));
+  for (int e = tid; e < G * cap; e += 1024) {
+    const int g = e / cap, r = e - g * cap;
+    const int len = min(cap, max(0, keep_count[seg0 + g]));
+    if (r < len) {
+      const int rel = keep_idx[(seg0 + g) * k + r];
+      kept[e] = scores[(seg0 + g) * k + min(max(rel, 0), k - 1)];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < G * cap; e += 1024) {
+    const int g = e / cap, r = e - g * cap;
+    const int len = min(cap, max(0, keep_count[seg0 + g]));
+    if (r >= len) continue;
+    const float s = kept[e];
+    int place = r;
+    for (int h = 0; h < G && place < post; ++h) {
+      if (h == g) continue;
+      const float* lst = kept + h * cap;
+      int lo = 0, hi = min(cap, max(0, keep_count[seg0 + h]));
+      // first position whose element does NOT go ahead of (g, r): ahead = score > s, or == s in a lower group
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float v = lst[mid];
+        if (v > s || (v == s && h < g)) lo = mid + 1; else hi = mid;
+      }
+      place += lo;
+    }
+    if (place < post) {
+      const int rel = min(max(keep_idx[(seg0 + g) * k + r], 0), k - 1);
+      const long long o = (long long)n * post + place;
+      out_boxes[o] = boxes[(seg0 + g) * k + rel];
+      out_scores[o] = s;
+      out_ids[o] = (long long)(g / A) * 1000 + (g % A);
+    }
+  }
+  if (tid == 0) out_count[n] = min(post, total);
+}
+
 }  // namespace
 
 extern "C" {
+
+int wsovod_rpn_group_topk(const float* logits, int B, int HW, int A, int pre_nms_topk, float* scores, long long* index,
+                          wsovod_stream_t stream) {
+  WS_CHECK_ARG(B >= 0 && HW >= 0 && A >= 0 && pre_nms_topk >= 1, "wsovod_rpn_group_topk: bad size");
+  if (pre_nms_topk > kTopkMax) {
+    wsovod::set_error("wsovod_rpn_group_topk: pre_nms_topk %d is above the %d pairs one workgroup sorts", pre_nms_topk,
+                      kTopkMax);
+    return WSOVOD_ERR_UNSUPPORTED;
+  }
+  if (B == 0 || HW == 0 || A == 0) return WSOVOD_OK;
+  WS_CHECK_ARG(logits && scores && index, "wsovod_rpn_group_topk: null pointer");
+  WS_CHECK_ARG((long long)B * A < (1ll << 31) && (long long)HW + 256 < (1ll << 31), "wsovod_rpn_group_topk: too large");
+  const int k = min(HW, pre_nms_topk);
+  static int slot = wsovod::prof_slot("rpn_group_topk");
+  hipStream_t s = (hipStream_t)stream;
+  wsovod::ProfScope prof(slot, s, 0.0, 6.0 * B * HW * A * 4 + 12.0 * B * A * k);
+  hipLaunchKernelGGL(rpn_group_topk_kernel, dim3(B * A), dim3(256), 0, s, logits, HW, A, k, scores, index);
+  WS_CHECK_LAUNCH("wsovod_rpn_group_topk");
+  return WSOVOD_OK;
+}
+
+int wsovod_nms_merge_groups(const float* boxes, const float* scores, const int* keep_idx, const int* keep_count,
+                            int num_images, int G, int A, int seg_len, int post_nms_topk, float* out_boxes,
+                            float* out_scores, long long* out_level_ids, int* out_count, wsovod_stream_t stream) {
+  WS_CHECK_ARG(num_images >= 0 && G >= 1 && A >= 1 && G % A == 0 && seg_len >= 0 && post_nms_topk >= 1,
+               "wsovod_nms_merge_groups: bad size");
+  if (num_images == 0) return WSOVOD_OK;
+  WS_CHECK_ARG(keep_count && out_count, "wsovod_nms_merge_groups: null pointer");
+  WS_CHECK_ARG(seg_len == 0 || (boxes && scores && keep_idx && out_boxes && out_scores && out_level_ids),
+               "wsovod_nms_merge_groups: null pointer");
+  WS_CHECK_ARG((((uintptr_t)boxes | (uintptr_t)out_boxes) & 15) == 0,
+               "wsovod_nms_merge_groups: boxes/out_boxes must be 16-byte aligned");
+  const int post = post_nms_topk, cap = max(1, min(post_nms_topk, seg_len));  // a list holds at most seg_len elements
+  const size_t lds = (size_t)G * cap * sizeof(float);
+  if (lds > 150 * 1024 || (long long)num_images * G * max(seg_len, 1) >= (1ll << 31)) {
+    wsovod::set_error("wsovod_nms_merge_groups: %d lists of up to %d kept scores need %zu B of LDS", G, cap, lds);
+    return WSOVOD_ERR_UNSUPPORTED;
+  }
+  if (lds > 64 * 1024)  // the opt-in is per device and cheap: asked for on every launch that needs it, no process-wide flag
+    WS_CHECK_HIP(hipFuncSetAttribute((const void*)nms_merge_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     150 * 1024), "wsovod_nms_merge_groups: LDS opt-in");
+  static int slot = wsovod::prof_slot("nms_merge_groups");
+  hipStream_t s = (hipStream_t)stream;
+  wsovod::ProfScope prof(slot, s, 0.0, (double)num_images * G * cap * 28.0);
+  hipLaunchKernelGGL(nms_merge_groups_kernel, dim3(num_images), dim3(1024), lds, s, (const float4*)boxes, scores,
+                     keep_idx, keep_count, G, A, max(seg_len, 1), cap, post, (float4*)out_boxes, out_scores, out_level_ids,
+                     out_count);
+  WS_CHECK_LAUNCH("wsovod_nms_merge_groups");
+  return WSOVOD_OK;
+}
 
 int wsovod_rpn_label_anchors(const float* anchors, int A, const float* gt_boxes, const int* gt_start,
                              const int* gt_count, int num_images, int total_gt, float thr_lo, float thr_hi, float* best_iou, int* best_gt,

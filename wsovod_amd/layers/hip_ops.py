@@ -1389,6 +1389,50 @@ def rpn_decode(anchors, deltas, index, image_sizes, weights, scale_clamp, min_si
     return boxes, valid.bool()
 
 
+RPN_GROUP_TOPK_MAX = 2048  # pairs one workgroup of wsovod_rpn_group_topk sorts in LDS; above it the torch route runs
+# top-k route of the MRRP RPN's proposal stage: "hip" (wsovod_rpn_group_topk) | "torch" (the stable sort it is compared with).
+# Default from profiles/mrrp_rpn_step.json by the project's rule: the stage's HIP median (0.855 / 1.393 ms at 1 / 8 images) is
+# below torch's (0.979 / 1.509) by less than the larger spread, so torch stays; WSOVOD_RPN_TOPK=hip
+# selects the kernel
+RPN_TOPK_ROUTE = __import__("os").environ.get("WSOVOD_RPN_TOPK", "torch")
+assert RPN_TOPK_ROUTE in ("hip", "torch"), f"WSOVOD_RPN_TOPK={RPN_TOPK_ROUTE}: hip | torch"
+
+
+def rpn_group_topk(logits, pre_nms_topk):
+    """logits (B, HW, A) f32 -> (scores (B, A, k), index (B, A, k) int64 = p * A + a), k = min(HW, pre_nms_topk): per
+    (row, anchor) the k best positions, torch's stable descending order bit for bit.  pre_nms_topk > 2048 raises."""
+    require_gpu(logits)
+    logits = logits.contiguous()
+    assert logits.dtype == torch.float32 and logits.dim() == 3
+    B, HW, A = logits.shape
+    k = min(HW, int(pre_nms_topk))
+    scores = torch.empty((B, A, k), dtype=torch.float32, device=logits.device)
+    index = torch.empty((B, A, k), dtype=torch.int64, device=logits.device)
+    check(lib().wsovod_rpn_group_topk(ptr(logits), B, HW, A, int(pre_nms_topk), ptr(scores), ptr(index), stream()),
+          "rpn_group_topk")
+    return scores, index
+
+
+def nms_merge_groups(boxes, scores, keep_idx, keep_count, num_images, G, A, seg_len, post_nms_topk):
+    """The per-image merge of nms_segments' kept lists over num_images * G segments of seg_len boxes each (segment
+    (n, g) at rows (n * G + g) * seg_len).  -> (boxes (N, post, 4), scores (N, post), level_ids (N, post) int64,
+    count (N) int32); rows past an image's count are zero."""
+    require_gpu(boxes, scores, keep_idx, keep_count)
+    boxes, scores = boxes.contiguous(), scores.contiguous()
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32
+    assert keep_idx.dtype == torch.int32 and keep_count.dtype == torch.int32
+    assert boxes.shape[0] == num_images * G * seg_len == scores.numel() and keep_count.numel() == num_images * G
+    post, dev = int(post_nms_topk), boxes.device
+    out_boxes = torch.zeros((num_images, post, 4), dtype=torch.float32, device=dev)
+    out_scores = torch.zeros((num_images, post), dtype=torch.float32, device=dev)
+    out_ids = torch.zeros((num_images, post), dtype=torch.int64, device=dev)
+    out_count = torch.zeros((num_images,), dtype=torch.int32, device=dev)
+    check(lib().wsovod_nms_merge_groups(ptr(boxes), ptr(scores), ptr(keep_idx.contiguous()), ptr(keep_count.contiguous()),
+                                        num_images, G, A, seg_len, post, ptr(out_boxes), ptr(out_scores), ptr(out_ids),
+                                        ptr(out_count), stream()), "nms_merge_groups")
+    return out_boxes, out_scores, out_ids, out_count
+
+
 def im2col_rows(x_nhwc, rows, kernel_size, stride=1, padding=0, dilation=1):
     """x (N,H,W,C) NHWC contiguous; rows (n) int64 flat output-pixel ids (negative -> zero row).
     Returns (n, k*k*C) patch rows, tap-major then channel."""

@@ -167,8 +167,26 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
             p.objectness_logits = torch.sigmoid(p.objectness_logits) * ramp
         self.rpn_proposals = proposals
         if loaded is not None:
+            for p1, p2 in zip(proposals, loaded):  # rcnn_wsovod.py:188-195 / :274-281 (the MRRP RPN tags its boxes)
+                if p1.has("level_ids"):
+                    p2.level_ids = self._loaded_level_ids(p1.level_ids, len(p2))
             proposals = [Instances.cat([p1, p2]) for p1, p2 in zip(proposals, loaded)]
         return proposals
+
+    def _loaded_level_ids(self, rpn_ids, num_loaded):
+        """Level ids of an image's loaded boxes: uniform integers in [min(rpn_ids), max(rpn_ids) + 1), the reference's
+        torch.randint(low_id, high_id, ...) with the bounds left on the device (tensor bounds there cost a host read).
+        An image without RPN boxes has no bounds to draw between: its loaded boxes get id 0 (branch 0), where the
+        reference's torch.min of an empty tensor raises."""
+        if len(rpn_ids) == 0:  # (a host-known length: the proposal stage's one read)
+            return torch.zeros((num_loaded,), dtype=torch.int64, device=rpn_ids.device)
+        low = rpn_ids.min()
+        span = rpn_ids.max() + 1 - low
+        return low + torch.minimum((self._level_id_draw(num_loaded, rpn_ids.device) * span).to(torch.int64), span - 1)
+
+    def _level_id_draw(self, num_loaded, device):
+        """Uniform [0, 1) numbers behind the loaded boxes' level ids.  Tests replace this to fix the draw."""
+        return torch.rand((num_loaded,), dtype=torch.float64, device=device)
 
     _step_meta = None  # set while a whole-step HIP graph is captured: the image-level labels are static input buffers
 

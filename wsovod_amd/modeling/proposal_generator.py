@@ -32,7 +32,8 @@ from .matcher import Matcher
 PROPOSAL_GENERATOR_REGISTRY = Registry("PROPOSAL_GENERATOR")
 RPN_HEAD_REGISTRY = Registry("RPN_HEAD")
 
-__all__ = ["StandardRPNHead", "WSOVODRPN_V2", "build_proposal_generator", "build_rpn_head", "find_top_rpn_proposals"]
+__all__ = ["StandardRPNHead", "WSOVODRPN_V2", "build_proposal_generator", "build_rpn_head", "find_top_rpn_proposals",
+           "find_top_rpn_proposals_group"]
 
 
 def _pad(n, m):
@@ -142,8 +143,10 @@ class StandardRPNHead(nn.Module):
         return {"in_channels": in_channels[0], "num_anchors": num_anchors[0], "box_dim": box_dim,
                 "conv_dims": cfg.MODEL.RPN.CONV_DIMS, "batch_rows": cfg.MODEL.RPN.BATCH_SIZE_PER_IMAGE}
 
-    def forward_nhwc(self, feature):
-        """feature: NCHW-logical / channels_last map -> ((N, H*W*A) logits, (N, H*W*A, 4) deltas), fp32."""
+    def forward_nhwc(self, feature, num_images=None):
+        """feature: NCHW-logical / channels_last map -> ((N, H*W*A) logits, (N, H*W*A, 4) deltas), fp32.
+        num_images: the images behind the N rows when the map stacks MRRP branches along N (N = L * num_images): the
+        anchor sample, and so the rows that carry a gradient, is per image, not per row."""
         x = feature.permute(0, 2, 3, 1)
         if not x.is_contiguous():
             x = x.contiguous()
@@ -151,7 +154,7 @@ class StandardRPNHead(nn.Module):
         A = self.num_anchors
         out = _RPNHeadFn.apply(x, self.conv, self.conv.weight, self.conv.bias, self.objectness_logits.weight,
                                self.objectness_logits.bias, self.anchor_deltas.weight, self.anchor_deltas.bias,
-                               N * self.batch_rows)
+                               (N if num_images is None else num_images) * self.batch_rows)
         logits = out[:, :A].reshape(N, Hh * Ww * A)
         deltas = out[:, A:5 * A].reshape(N, Hh * Ww * A, 4)
         return logits, deltas
@@ -207,6 +210,78 @@ def find_top_rpn_proposals(anchors: List[Boxes], pred_objectness_logits: List[to
     return results
 
 
+def _group_topk_torch(logits, k):
+    """The comparator of H.rpn_group_topk and the route past its limit: proposal_utils.py:205-225 for every
+    (row, anchor) at once, with a stable sort.  logits (B, HW, A) -> scores (B, A, k), flat index p * A + a (B, A, k)."""
+    B, HW, A = logits.shape
+    sc, pos = torch.sort(logits.permute(0, 2, 1), dim=-1, descending=True, stable=True)
+    idx = pos[..., :k] * A + torch.arange(A, device=logits.device).view(1, A, 1)
+    return sc[..., :k].contiguous(), idx.contiguous()
+
+
+def rpn_group_topk(logits, k):
+    """The k best positions of every (row, anchor): the HIP radix select, or torch's stable sort when
+    WSOVOD_RPN_TOPK=torch or k is past the kernel's limit (both give the same bits)."""
+    if H.RPN_TOPK_ROUTE == "hip" and k <= H.RPN_GROUP_TOPK_MAX and logits.is_cuda:
+        return H.rpn_group_topk(logits, k)
+    return _group_topk_torch(logits, k)
+
+
+def find_top_rpn_proposals_group(anchors: List[Boxes], pred_objectness_logits: List[torch.Tensor],
+                                 pred_anchor_deltas: List[torch.Tensor], image_sizes: List[Tuple[int, int]],
+                                 num_anchors: List[int], box2box_transform, nms_thresh: float, pre_nms_topk: int,
+                                 post_nms_topk: int, min_box_size: float, training: bool):
+    """proposal_utils.py:147-363 with the decode of rpn.py:495-515 folded in.  For every level l and anchor id a: the
+    min(H*W, pre_nms_topk) best of that anchor's H*W logits, tagged l * 1000 + a; per image: non-finite boxes / scores
+    dropped (raise in training), clip, min-size test, NMS inside every (level, anchor) group, the first post_nms_topk of
+    the survivors by score.  One top-k launch over all L * N rows, one decode per level (the anchors differ), one NMS
+    over the N * L * A segments, one merge per image, ONE host read (counts + non-finite flag).
+    As find_top_rpn_proposals, the training-time raise is stricter than the reference's: a non-finite delta ANYWHERE raises
+    (one reduction over each level's deltas), where the reference looks at the selected rows only.
+    Returns list[Instances{proposal_boxes, objectness_logits, level_ids (int64)}] sorted by score."""
+    L, N = len(anchors), len(image_sizes)
+    A = num_anchors[0]
+    assert all(a == A for a in num_anchors) and len(pred_objectness_logits) == L == len(pred_anchor_deltas)
+    dev = pred_objectness_logits[0].device
+    HW = pred_objectness_logits[0].shape[1] // A
+    assert all(lo.shape == (N, HW * A) for lo in pred_objectness_logits), "the MRRP levels share one map size"
+    sizes_t = H.const_tensor([float(v) for hw in image_sizes for v in hw], torch.float32, dev).view(-1, 2)
+    logits = torch.stack([lo.detach() for lo in pred_objectness_logits]).view(L * N, HW, A)  # row l * N + n
+    k = min(HW, pre_nms_topk)
+    scores, index = rpn_group_topk(logits, k)  # (L*N, A, k)
+    boxes, valid, bad = [], [], ~torch.isfinite(scores).all()
+    for l in range(L):
+        deltas_l = pred_anchor_deltas[l].detach()
+        b, v = H.rpn_decode(anchors[l].tensor, deltas_l, index[l * N:(l + 1) * N].reshape(N, A * k), sizes_t,
+                            box2box_transform.weights, box2box_transform.scale_clamp, min_box_size)
+        boxes.append(b)
+        valid.append(v)
+        bad = bad | ~torch.isfinite(deltas_l).all()
+    G = L * A
+    boxes = torch.stack(boxes, dim=1).view(N * G * k, 4)  # segment (n, l, a) = rows [(n * G + l * A + a) * k, ... + k)
+    scores = scores.view(L, N, A * k).permute(1, 0, 2).reshape(N * G * k)
+    valid = torch.stack(valid, dim=1).view(N * G * k) & torch.isfinite(scores)
+    seg = H.const_tensor([i * k for i in range(N * G + 1)], torch.int32, dev)
+    keep, count = H.nms_segments(boxes, seg, k, nms_thresh, post_nms_topk, valid=valid)
+    out_boxes, out_scores, out_ids, out_count = H.nms_merge_groups(boxes, scores, keep, count, N, G, A, k, post_nms_topk)
+    host = torch.cat([out_count, bad.to(torch.int32).view(1)]).tolist()  # the one host read of this stage
+    if training and host[-1]:
+        raise FloatingPointError("Predicted boxes or scores contain Inf/NaN. Training has diverged.")
+    results = []
+    for n, image_size in enumerate(image_sizes):
+        res = Instances(image_size)
+        res.proposal_boxes = Boxes(out_boxes[n, :host[n]])
+        res.objectness_logits = out_scores[n, :host[n]]
+        res.level_ids = out_ids[n, :host[n]]
+        results.append(res)
+    return results
+
+
+_MRRP_RPN_IS_OPT_IN = ("the MRRP RPN (per-branch anchors, per-level top-k, level_id * 1000 + anchor_id) is built only with "
+                       "MODEL.HIP.MRRP_RPN: True (hot_path_*_mrrp_rpn.yaml); without that key MODEL.MRRP.MRRP_ON runs with "
+                       "precomputed proposals only")
+
+
 @PROPOSAL_GENERATOR_REGISTRY.register()
 class WSOVODRPN_V2(nn.Module):
     """rpn.py:90-515.  Trained from the ROI heads' pseudo ground truth: `forward` keeps the predictions,
@@ -218,11 +293,16 @@ class WSOVODRPN_V2(nn.Module):
                  pre_nms_topk: Tuple[float, float], post_nms_topk: Tuple[float, float], nms_thresh: float = 0.7,
                  min_box_size: float = 0.0, anchor_boundary_thresh: float = -1.0,
                  loss_weight: Union[float, Dict[str, float]] = 1.0, box_reg_loss_type: str = "smooth_l1",
-                 smooth_l1_beta: float = 0.0, mrrp_on: bool = False, mrrp_num_branch: int = 3, mrrp_fast: bool = False):
+                 smooth_l1_beta: float = 0.0, mrrp_on: bool = False, mrrp_num_branch: int = 3, mrrp_fast: bool = False,
+                 hip_mrrp_rpn: bool = False):
         super().__init__()
-        if mrrp_on:
-            raise NotImplementedError("the MRRP RPN (per-branch anchors, per-level top-k, level_id * 1000 + anchor_id) is the next step "
-                                      "after the MRRP VGG backbone and heads: MODEL.MRRP.MRRP_ON runs with precomputed proposals only")
+        if mrrp_on and not hip_mrrp_rpn:
+            raise NotImplementedError(_MRRP_RPN_IS_OPT_IN)
+        if mrrp_on and mrrp_fast:
+            raise NotImplementedError("wsovod_amd: MODEL.MRRP.TEST_BRANCH_IDX != -1 (mrrp_fast) with the MRRP RPN: every shipped "
+                                      "MRRP config sets -1 (all branches at test time)")
+        if mrrp_on and not 1 <= mrrp_num_branch <= 4:
+            raise NotImplementedError(f"the MRRP RPN runs 1 to 4 branches (MODEL.MRRP.NUM_BRANCH = {mrrp_num_branch})")
         if box_reg_loss_type != "smooth_l1":
             raise NotImplementedError(f"RPN.BBOX_REG_LOSS_TYPE={box_reg_loss_type}: shipped configs use smooth_l1")
         self.in_features = in_features
@@ -242,7 +322,7 @@ class WSOVODRPN_V2(nn.Module):
         self.loss_weight = loss_weight
         self.box_reg_loss_type = box_reg_loss_type
         self.smooth_l1_beta = smooth_l1_beta
-        self.mrrp_on = False
+        self.mrrp_on, self.mrrp_num_branch = bool(mrrp_on), int(mrrp_num_branch)
 
     @classmethod
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):
@@ -252,6 +332,11 @@ class WSOVODRPN_V2(nn.Module):
             raise KeyError(f"MODEL.RPN.IN_FEATURES = {list(in_features)} names {missing}, which the backbone "
                            f"{cfg.MODEL.BACKBONE.NAME} does not return; available features: {sorted(input_shape)}")
         shapes = [input_shape[f] for f in in_features]
+        if cfg.MODEL.MRRP.MRRP_ON and not cfg.MODEL.HIP.MRRP_RPN:  # (before per-level SIZES meet a one-level generator)
+            raise NotImplementedError(_MRRP_RPN_IS_OPT_IN)
+        if cfg.MODEL.MRRP.MRRP_ON:  # rpn.py:201-213: one level per branch (per-level SIZES)
+            assert len(shapes) == 1, "the MRRP RPN reads one branch-major feature map"
+            shapes = shapes * cfg.MODEL.MRRP.NUM_BRANCH
         return {
             "in_features": in_features,
             "min_box_size": cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE,
@@ -265,7 +350,7 @@ class WSOVODRPN_V2(nn.Module):
             "box_reg_loss_type": cfg.MODEL.RPN.BBOX_REG_LOSS_TYPE,
             "smooth_l1_beta": cfg.MODEL.RPN.SMOOTH_L1_BETA,
             "mrrp_on": cfg.MODEL.MRRP.MRRP_ON, "mrrp_num_branch": cfg.MODEL.MRRP.NUM_BRANCH,
-            "mrrp_fast": cfg.MODEL.MRRP.TEST_BRANCH_IDX != -1,
+            "mrrp_fast": cfg.MODEL.MRRP.TEST_BRANCH_IDX != -1, "hip_mrrp_rpn": cfg.MODEL.HIP.MRRP_RPN,
             "pre_nms_topk": (cfg.MODEL.RPN.PRE_NMS_TOPK_TRAIN, cfg.MODEL.RPN.PRE_NMS_TOPK_TEST),
             "post_nms_topk": (cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN, cfg.MODEL.RPN.POST_NMS_TOPK_TEST),
             "anchor_generator": build_anchor_generator(cfg, shapes),
@@ -376,12 +461,23 @@ class WSOVODRPN_V2(nn.Module):
     def forward(self, images: ImageList, features: Dict[str, torch.Tensor],
                 gt_instances: Optional[List[Instances]] = None):
         features = [features[f] for f in self.in_features]
-        anchors = self.anchor_generator(features)
-        pred_objectness_logits, pred_anchor_deltas = [], []
-        for f in features:
-            lo, de = self.rpn_head.forward_nhwc(f)
-            pred_objectness_logits.append(lo)
-            pred_anchor_deltas.append(de)
+        if self.mrrp_on:
+            # rpn.py:398-400: the branch-major (L*N, C, H, W) map is L levels of N images.  The head's weights are shared,
+            # so ONE call on the whole map is the L calls; row l * N + n of its result is level l of image n
+            f, L = features[0], self.mrrp_num_branch
+            N = f.shape[0] // L
+            assert len(features) == 1 and f.shape[0] == L * N and N == len(images.image_sizes), tuple(f.shape)
+            anchors = self.anchor_generator([f] * L)
+            lo, de = self.rpn_head.forward_nhwc(f, num_images=N)
+            pred_objectness_logits = list(lo.view(L, N, -1).unbind(0))  # L x (N, H*W*A): cat(dim=1) = level order
+            pred_anchor_deltas = list(de.view(L, N, -1, 4).unbind(0))
+        else:
+            anchors = self.anchor_generator(features)
+            pred_objectness_logits, pred_anchor_deltas = [], []
+            for f in features:
+                lo, de = self.rpn_head.forward_nhwc(f)
+                pred_objectness_logits.append(lo)
+                pred_anchor_deltas.append(de)
         if self.training:
             self.anchors = anchors
             self.pred_objectness_logits = pred_objectness_logits
@@ -401,6 +497,11 @@ class WSOVODRPN_V2(nn.Module):
 
     @torch.no_grad()
     def predict_proposals(self, anchors, pred_objectness_logits, pred_anchor_deltas, image_sizes):
+        if self.mrrp_on:
+            return find_top_rpn_proposals_group(anchors, pred_objectness_logits, pred_anchor_deltas, image_sizes,
+                                                self.anchor_generator.num_anchors, self.box2box_transform, self.nms_thresh,
+                                                self.pre_nms_topk[self.training], self.post_nms_topk[self.training],
+                                                self.min_box_size, self.training)
         return find_top_rpn_proposals(anchors, pred_objectness_logits, pred_anchor_deltas, image_sizes,
                                       self.box2box_transform, self.nms_thresh, self.pre_nms_topk[self.training],
                                       self.post_nms_topk[self.training], self.min_box_size, self.training)

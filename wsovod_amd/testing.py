@@ -18,11 +18,12 @@ def hot_path_cfg(depth=18, K=20, D=512, precision="bf16", pooler="ROIPool", devi
     that the hot path reads, with PROPOSAL_GENERATOR=PrecomputedProposals, BBOX_REFINE off.
     backbone="vgg16": WSOVOD_V_16_DC5_1x instead (hot_path_vgg16.yaml; `depth` is not read); with mrrp its MRRP form
     (hot_path_vgg16_mrrp.yaml: precomputed proposals only).  backbone="resnet" with mrrp: WSOVOD_MRRP_WSR_{18,50}_DC5_1x
-    (hot_path_r{18,50}_mrrp.yaml: precomputed proposals only)."""
+    (hot_path_r{18,50}_mrrp.yaml: precomputed proposals only).  mrrp with rpn: the shipped form of those three, the MRRP RPN
+    next to the loaded proposals (hot_path_{vgg16,r18,r50}_mrrp_rpn.yaml, MODEL.HIP.MRRP_RPN on)."""
     cfg = get_cfg()
     if mrrp:
-        assert backbone in ("vgg16", "resnet") and not rpn, "the MRRP hot paths run with precomputed proposals"
-        name = "hot_path_vgg16_mrrp.yaml" if backbone == "vgg16" else f"hot_path_r{depth}_mrrp.yaml"
+        assert backbone in ("vgg16", "resnet"), backbone
+        name = ("hot_path_vgg16_mrrp" if backbone == "vgg16" else f"hot_path_r{depth}_mrrp") + ("_rpn.yaml" if rpn else ".yaml")
         cfg.merge_from_file(os.path.join(_CONFIG_DIR, name))
     elif backbone == "vgg16":
         cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_rpn.yaml" if rpn else "hot_path_vgg16.yaml"))

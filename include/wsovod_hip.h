@@ -641,6 +641,55 @@ int wsovod_pgt_mine_and_label(const float* scores, long long ld_scores, const fl
                               long long* out_classes, float* out_boxes, float* out_scores,
                               float* out_weights, int* out_matched, wsovod_stream_t stream);
 
+/* MIST pseudo-ground-truth mining (WSOVOD.INSTANCE_REFINEMENT.REFINE_MIST), no grad, in three entry points around
+ * wsovod_nms_segments; nothing is read back by the host in between.  Shared layout: image g owns the class slots
+ * [gt_offsets[g], gt_offsets[g+1]) of gt_classes_img (as for wsovod_pgt_mine_and_label; T slots in all), slot t owns the
+ * list rows [t * k_cap, (t+1) * k_cap), so image g owns the rows [gt_offsets[g] * k_cap, gt_offsets[g+1] * k_cap) of
+ * every (T * k_cap)-row array below.  k_cap = max(int(R_max * top_pro), 1), R_max the longest image: a host integer.
+ *
+ * wsovod_mist_select.  Replaces get_pgt_top_k as get_pgt_mist calls it (roi_heads.py:919-928 -> :1089-1179; top_k =
+ * top_pro in (0, 1), thres > 0, boxes (R,4)).  Per slot: n = rows of the image with box area > 20 (:1090-1096);
+ * k = max((int)((double)n * top_pro), 1) (:1119, Python's int of a double product); the k largest of the slot's score
+ * column over those rows (:1122-1125), descending, equal scores by ascending row, with wsovod_rpn_group_topk's order and
+ * equality; rank 0 and every further rank with score >= thres are kept (:1148-1154).
+ *   scores (M, ld_scores >= K) f32; sel_scores / sel_index (T * k_cap): the kept ranks in order, sel_index = the row
+ *   inside its image; sel_len (T): how many (0 when no row of the image is valid).
+ * k_cap > 2048 is refused (WSOVOD_ERR_UNSUPPORTED): one workgroup sorts the selected pairs in LDS. */
+int wsovod_mist_select(const float* scores, long long ld_scores, const float* boxes, const int* seg_offsets, int G,
+                       const long long* gt_classes_img, const int* gt_offsets, int T, int K, double top_pro, float thres,
+                       int k_cap, float* sel_scores, int* sel_index, int* sel_len, wsovod_stream_t stream);
+
+/* wsovod_mist_merge.  Replaces the flattening of the kept (rank, class) entries (roi_heads.py:1155-1179) and the score
+ * sort inside batched_nms (:931-935, all category ids zero): the image's lists merged into one list by descending score;
+ * equal scores by ascending rank, then ascending class slot (the row-major flattening order).
+ *   cand_boxes (T*k_cap, 4), cand_scores, cand_classes (int64), cand_index (int32 row inside the image),
+ *   cand_valid (uint8): image g's candidates from row gt_offsets[g] * k_cap on; the rows between cand_count[g] and the
+ *   image's capacity are zero with cand_valid 0 (cand_index -1).  nms_seg_offsets (G+1) = gt_offsets * k_cap: with
+ *   cand_valid, the segments wsovod_nms_segments is then called on.  max_classes: the longest class list (host integer;
+ *   max_classes * k_cap keys are staged in LDS, above 64 KiB: WSOVOD_ERR_UNSUPPORTED). */
+int wsovod_mist_merge(const float* sel_scores, const int* sel_index, const int* sel_len, const float* boxes,
+                      const int* seg_offsets, const long long* gt_classes_img, const int* gt_offsets, int G, int T,
+                      int max_classes, int k_cap, float* cand_boxes, float* cand_scores, long long* cand_classes,
+                      int* cand_index, unsigned char* cand_valid, int* cand_count, int* nms_seg_offsets,
+                      wsovod_stream_t stream);
+
+/* wsovod_mist_label.  Replaces the target construction of get_pgt_mist (roi_heads.py:936-939, :1027-1038) and
+ * label_and_sample_proposals_wsl (:1722-1825) with Matcher([thr], [0, 1]).  keep_idx / keep_count: what
+ * wsovod_nms_segments wrote for the segments of wsovod_mist_merge.  Image g's targets = its kept candidates in order, at
+ * rows gt_offsets[g] * k_cap ... of pgt_* (pgt_weights = pgt_scores, :1035-1037; pgt_index = the proposal's row inside
+ * the image), pgt_count[g] of them; an image without a candidate gets the one dummy target of :1181-1207 (box
+ * [-1e4, -1e4, 1e4, 1e4], class 0, score and weight 1, index -1).  An image with NO class slot (gt_offsets[g] ==
+ * gt_offsets[g+1]) owns no row: its proposals are labelled against that dummy, its pgt_count is 0.  Every proposal takes the target of maximal IoU
+ * (detectron2 pairwise_iou; first maximum in target order), label = its class if IoU >= iou_threshold else K, and
+ * carries its box / score / weight; out_matched = the target's position in the image's list.  Any number of targets:
+ * they pass through LDS 128 at a time.  max_rows = the longest image (launch geometry only). */
+int wsovod_mist_label(const float* boxes, const int* seg_offsets, int G, int max_rows, const int* gt_offsets, int k_cap,
+                      const float* cand_boxes, const float* cand_scores, const long long* cand_classes,
+                      const int* cand_index, const int* cand_count, const int* keep_idx, const int* keep_count, int K,
+                      float iou_threshold, float* pgt_boxes, long long* pgt_classes, float* pgt_scores,
+                      float* pgt_weights, int* pgt_index, int* pgt_count, long long* out_classes, float* out_boxes,
+                      float* out_scores, float* out_weights, int* out_matched, wsovod_stream_t stream);
+
 /* Proposal sub-sampling for the refinement losses, no grad.  Replaces detectron2 `subsample_labels` as called by
  * WSOVODROIHeads._sample_proposals_wsl (roi_heads.py:1566-1603) when an image has more proposals than
  * WSOVOD.SAMPLING.BATCH_SIZE_PER_IMAGE or POSITIVE_FRACTION < 1 (the shipped RPN configs: up to 4000 loaded + 1024

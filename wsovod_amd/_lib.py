@@ -143,6 +143,9 @@ SIGNATURES = {
     "wsovod_rpn_decode": [_P, _P, _P, _I, _I, _L, _P, C.POINTER(C.c_float), _F, _F, _P, _P, _P],
     "wsovod_rpn_group_topk": [_P, _I, _I, _I, _I, _P, _P, _P],
     "wsovod_nms_merge_groups": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "wsovod_mist_select": [_P, _L, _P, _P, _I, _P, _P, _I, _I, C.c_double, _F, _I, _P, _P, _P, _P],
+    "wsovod_mist_merge": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "wsovod_mist_label": [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _F] + [_P] * 11 + [_P],
 }
 
 class SgdTensor(C.Structure):

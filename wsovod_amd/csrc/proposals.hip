@@ -18,6 +18,7 @@
 //                           sequential dependency per row is one scalar bit test.  Kept positions are written in
 //                           order (they stay sorted by score) and the scan stops at max_keep.
 #include "common.h"
+#include "topk_select.h"
 
 // Index results (bins, keep sets, labels) must match the reference bit for bit: no mul+add fusion anywhere in this
 // file (HIP's __fmul_rn & co. are plain operators and would still be contracted under the default fp-contract=fast).
@@ -244,121 +245,19 @@ __global__ __launch_bounds__(256) void rpn_label_kernel(const float4* __restrict
 // ---- grouped top-k of the MRRP RPN (proposal_utils.py:199-239: per level and per anchor id, sort the H*W logits of
 // that anchor and keep min(H*W, pre_nms_topk)) ------------------------------------------------------------------------
 // One workgroup per (row b, anchor a); the row is the HW values logits[b][p][a], stride A.  Order and equality are
-// torch.sort's (descending, stable): every NaN is one value above +inf, -0.0 == +0.0, equal values by position ascending.
-//   1. radix select of the k-th largest over order-preserving 32-bit keys, four 8-bit digits from the top; every wavefront
-//      owns one contiguous quarter of the row and its own LDS histogram, the row is re-read (L2) on each pass
-//   2. compaction into LDS: every key above the threshold, plus the first `ties` keys equal to it by position (the
-//      per-wavefront counts of the last histogram give each quarter its base, so the walk needs no barrier)
-//   3. bitonic sort of the <= 2048 (key, ~position) words in LDS, then coalesced stores of score and flat index p * A + a
-constexpr int kTopkMax = 2048;
-
-__device__ __forceinline__ unsigned int topk_key(float x) {
-  if (x != x) return 0xffffffffu;          // every NaN: one value, above +inf
-  if (x == 0.f) return 0x80000000u;        // -0.0 == +0.0
-  const unsigned int u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// torch.sort's (descending, stable); selection and sort are topk_select.h's, then coalesced stores of score and flat
+// index p * A + a.
 __global__ __launch_bounds__(256) void rpn_group_topk_kernel(const float* __restrict__ logits, int HW, int A, int k,
                                                              float* __restrict__ out_scores,
                                                              long long* __restrict__ out_index) {
-  __shared__ unsigned long long items[kTopkMax];  // (key << 32) | ~position: descending = key desc, position asc
-  __shared__ unsigned int hist[4][256];
-  __shared__ unsigned int sel[2];                 // digit chosen by the current pass, what remains of k below it
-  __shared__ unsigned int wave_eq[4];             // keys equal to the threshold in each wavefront's quarter
-  __shared__ unsigned int n_above;                // compaction cursor of the keys above the threshold
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ TopkShared sh;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x / A, a = blockIdx.x - b * A;
   const float* row = logits + ((long long)b * HW) * A + a;
-  const int Q = ceil_div(ceil_div(HW, 4), 64) * 64;
-  const int p_begin = min(HW, wave * Q), p_end = min(HW, p_begin + Q);
-
-  unsigned int prefix = 0u, pmask = 0u, rem = (unsigned int)k;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    for (int i = tid; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0u;
-    __syncthreads();
-    for (int p0 = p_begin; p0 < p_end; p0 += 64) {
-      const int p = p0 + lane;
-      if (p < p_end) {
-        const unsigned int key = topk_key(row[(long long)p * A]);
-        if ((key & pmask) == prefix) atomicAdd(&hist[wave][(key >> shift) & 255u], 1u);
-      }
-    }
-    __syncthreads();
-    if (wave == 0) {  // lane l owns the digits 255 - 4l .. 252 - 4l: counts above each digit by a 64-lane scan
-      unsigned int c[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int d = 255 - (4 * lane + j);
-        c[j] = hist[0][d] + hist[1][d] + hist[2][d] + hist[3][d];
-      }
-      const unsigned int mine = c[0] + c[1] + c[2] + c[3];
-      unsigned int incl = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-      }
-      unsigned int above = incl - mine;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (above < rem && rem <= above + c[j]) {  // exactly one (lane, j): 1 <= rem <= the pass's total
-          sel[0] = 255u - (unsigned int)(4 * lane + j);
-          sel[1] = rem - above;
-        }
-        above += c[j];
-      }
-    }
-    __syncthreads();
-    const unsigned int d = sel[0];
-    rem = sel[1];
-    prefix |= d << shift;
-    pmask |= 255u << shift;
-    if (pass == 3 && tid < 4) wave_eq[tid] = hist[tid][d];
-    if (pass == 3 && tid == 0) n_above = 0u;
-    __syncthreads();
-  }
-  // prefix = the k-th largest key; rem = how many keys equal to it belong to the result (the first by position)
-  const unsigned int thr = prefix, ties = rem, above_total = (unsigned int)k - ties;
-  unsigned int eq_seen = 0u;
-  for (int w = 0; w < wave; ++w) eq_seen += wave_eq[w];
-  int n_sort = 1;
-  while (n_sort < k) n_sort <<= 1;
-  for (int i = k + tid; i < n_sort; i += 256) items[i] = 0ull;  // padding: below every real key, after every position
-  for (int p0 = p_begin; p0 < p_end; p0 += 64) {
-    const int p = p0 + lane;
-    const unsigned int key = p < p_end ? topk_key(row[(long long)p * A]) : 0u;
-    const bool gt = p < p_end && key > thr, eq = p < p_end && key == thr;
-    const unsigned long long m_gt = __ballot(gt), m_eq = __ballot(eq);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned int base = 0u;
-    if (lane == 0 && m_gt) base = atomicAdd(&n_above, (unsigned int)__popcll(m_gt));
-    base = __shfl(base, 0, 64);
-    unsigned int slot = 0xffffffffu;
-    if (gt) slot = base + (unsigned int)__popcll(m_gt & below);
-    if (eq) {
-      const unsigned int r = eq_seen + (unsigned int)__popcll(m_eq & below);
-      if (r < ties) slot = above_total + r;
-    }
-    if (slot < (unsigned int)k) items[slot] = ((unsigned long long)key << 32) | (unsigned int)~(unsigned int)p;
-    eq_seen += (unsigned int)__popcll(m_eq);
-  }
-  for (int size = 2; size <= n_sort; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = tid; i < (n_sort >> 1); i += 256) {
-        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-        const unsigned long long x = items[lo], y = items[hi];
-        const bool desc = (lo & size) == 0;
-        if (desc ? x < y : x > y) { items[lo] = y; items[hi] = x; }
-      }
-    }
-  }
-  __syncthreads();
+  topk_select_sort([&](int p) { return topk_key(row[(long long)p * A]); }, HW, k, sh);
   const long long out0 = (long long)blockIdx.x * k;
   for (int t = tid; t < k; t += 256) {
-    const unsigned int p = ~(unsigned int)(items[t] & 0xffffffffull);
+    const unsigned int p = ~(unsigned int)(sh.items[t] & 0xffffffffull);
     out_scores[out0 + t] = row[(long long)p * A];  // the value itself: the key folds -0.0 and the NaN payloads
     out_index[out0 + t] = (long long)p * A + a;
   }

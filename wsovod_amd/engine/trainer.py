@@ -980,6 +980,12 @@ class HotPathTrainer:
         if PROFILING[0]:  # the per-launch profiler needs the launches
             return None
         rh = m.roi_heads
+        if getattr(rh, "refine_mist", False):
+            # MIST sizes its candidate and target rows by this step's longest image and longest class list (host ints, no
+            # device read).  A captured graph's static layout would have to provision K class lists for every image, which
+            # at K = 80 is beyond what one NMS segment holds; nobody has built or measured that.  MIST steps keep the eager
+            # launches
+            return None
         rows = self.row_bucket(sum(len(x["proposals"]) for x in data))
         # every row is kept by the refinement sampling (no random sub-sample inside the step): the shipped hot-path setting
         if not getattr(rh, "sampling_on", False) or rows > min(rh.batch_size_per_images[:rh.refine_K] or [0]) \

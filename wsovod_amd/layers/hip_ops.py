@@ -1226,6 +1226,116 @@ def pgt_mine_and_label(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, i
     return o
 
 
+# get_pgt_mist's constants (roi_heads.py:915, :924, :933): share of the valid proposals per class, score floor, NMS IoU
+MIST_TOP_PRO, MIST_THRES, MIST_NMS_IOU = 0.15, 0.05, 0.2
+MIST_K_CAP_MAX = 2048      # == kTopkMax (csrc/topk_select.h): pairs one workgroup of wsovod_mist_select sorts in LDS
+# boxes one segment of wsovod_nms_segments may hold (csrc/proposals.hip): its scan stages two chunks of 64 rows x W = ceil(n / 64)
+# 64-bit words in at most 159 KiB of LDS -> W <= 159; the 64 * 64 * kScanRegs = 16384 of its register bitmap is never reached
+NMS_SEGMENT_MAX = 159 * 64
+
+
+def mist_k(n, top_pro=MIST_TOP_PRO):
+    """Candidates per class among n valid proposals: max(int(n * top_pro), 1) (roi_heads.py:1119).  The kernel computes
+    the same from its own count as (int)((double)n * top_pro); with n = the longest image this is the lists' capacity."""
+    return max(int(int(n) * float(top_pro)), 1)
+
+
+def mist_select(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, K, k_cap, top_pro=MIST_TOP_PRO, thres=MIST_THRES):
+    """See include/wsovod_hip.h.  scores (M, >= K) f32 with a contiguous last dim (a column block of a wider matrix is
+    fine).  -> (sel_scores (T, k_cap), sel_index (T, k_cap) int32, sel_len (T) int32); k_cap > 2048 raises."""
+    require_gpu(scores, boxes, seg_offsets, gt_classes_img, gt_offsets)
+    assert scores.dtype == torch.float32 and boxes.dtype == torch.float32 and boxes.is_contiguous()
+    assert seg_offsets.dtype == torch.int32 and gt_offsets.dtype == torch.int32 and gt_classes_img.dtype == torch.int64
+    dev, T, G = scores.device, gt_classes_img.numel(), seg_offsets.numel() - 1
+    sel_scores = torch.zeros((T, int(k_cap)), dtype=torch.float32, device=dev)
+    sel_index = torch.zeros((T, int(k_cap)), dtype=torch.int32, device=dev)
+    sel_len = torch.zeros((T,), dtype=torch.int32, device=dev)
+    check(lib().wsovod_mist_select(ptr(scores), _ld(scores), ptr(boxes), ptr(seg_offsets), G, ptr(gt_classes_img),
+                                   ptr(gt_offsets), T, int(K), C.c_double(top_pro), C.c_float(thres), int(k_cap),
+                                   ptr(sel_scores), ptr(sel_index), ptr(sel_len), stream()), "mist_select")
+    return sel_scores, sel_index, sel_len
+
+
+def mist_merge(sel_scores, sel_index, sel_len, boxes, seg_offsets, gt_classes_img, gt_offsets, max_classes):
+    """See include/wsovod_hip.h.  -> dict of the capacity-padded candidate arrays (T * k_cap rows), the per-image count
+    and the (G+1) segment offsets wsovod_nms_segments takes."""
+    require_gpu(sel_scores, sel_index, sel_len, boxes, seg_offsets, gt_classes_img, gt_offsets)
+    dev, (T, k_cap), G = boxes.device, sel_scores.shape, seg_offsets.numel() - 1
+    N = T * k_cap
+    c = dict(boxes=torch.empty((N, 4), dtype=torch.float32, device=dev),
+             scores=torch.empty((N,), dtype=torch.float32, device=dev),
+             classes=torch.empty((N,), dtype=torch.int64, device=dev),
+             index=torch.empty((N,), dtype=torch.int32, device=dev),
+             valid=torch.zeros((N,), dtype=torch.uint8, device=dev),
+             count=torch.zeros((G,), dtype=torch.int32, device=dev),
+             seg=torch.zeros((G + 1,), dtype=torch.int32, device=dev), k_cap=k_cap)
+    check(lib().wsovod_mist_merge(ptr(sel_scores), ptr(sel_index), ptr(sel_len), ptr(boxes), ptr(seg_offsets),
+                                  ptr(gt_classes_img), ptr(gt_offsets), G, T, int(max_classes), k_cap, ptr(c["boxes"]),
+                                  ptr(c["scores"]), ptr(c["classes"]), ptr(c["index"]), ptr(c["valid"]), ptr(c["count"]),
+                                  ptr(c["seg"]), stream()), "mist_merge")
+    return c
+
+
+def mist_label(boxes, seg_offsets, gt_offsets, max_rows, cand, keep_idx, keep_count, K, iou_threshold):
+    """See include/wsovod_hip.h.  cand: what mist_merge returned; keep_idx / keep_count: nms_segments' result on it.
+    -> the dict pgt_mine_and_label returns, with (T * k_cap)-row pgt_* arrays: image g's targets are the rows
+    [pgt_start[g], pgt_start[g] + pgt_count[g])."""
+    require_gpu(boxes, seg_offsets, gt_offsets, keep_idx, keep_count)
+    dev, M, G, k_cap = boxes.device, boxes.size(0), seg_offsets.numel() - 1, cand["k_cap"]
+    N = cand["scores"].numel()
+    zero = torch.zeros((32 * N + 4 * G,), dtype=torch.uint8, device=dev)  # one fill for the five zero-initialised outputs
+    o = dict(
+        pgt_boxes=zero[:16 * N].view(torch.float32).view(N, 4),
+        pgt_classes=zero[16 * N:24 * N].view(torch.int64),
+        pgt_scores=zero[24 * N:28 * N].view(torch.float32),
+        pgt_weights=zero[28 * N:32 * N].view(torch.float32),
+        pgt_index=torch.full((N,), -1, dtype=torch.int32, device=dev),
+        pgt_count=zero[32 * N:].view(torch.int32),
+        pgt_start=cand["seg"][:G],
+        gt_classes=torch.full((M,), -1, dtype=torch.int64, device=dev) if _TAIL.rows_true is not None
+        else torch.empty((M,), dtype=torch.int64, device=dev),
+        gt_boxes=_alloc((M, 4), torch.float32, dev),
+        gt_scores=_alloc((M,), torch.float32, dev),
+        gt_weights=_alloc((M,), torch.float32, dev),
+        matched=_alloc((M,), torch.int32, dev),
+    )
+    check(lib().wsovod_mist_label(
+        ptr(boxes), ptr(seg_offsets), G, int(max_rows), ptr(gt_offsets), k_cap, ptr(cand["boxes"]), ptr(cand["scores"]),
+        ptr(cand["classes"]), ptr(cand["index"]), ptr(cand["count"]), ptr(keep_idx), ptr(keep_count), int(K),
+        C.c_float(iou_threshold), ptr(o["pgt_boxes"]), ptr(o["pgt_classes"]), ptr(o["pgt_scores"]), ptr(o["pgt_weights"]),
+        ptr(o["pgt_index"]), ptr(o["pgt_count"]), ptr(o["gt_classes"]), ptr(o["gt_boxes"]), ptr(o["gt_scores"]),
+        ptr(o["gt_weights"]), ptr(o["matched"]), stream()), "mist_label")
+    return o
+
+
+def mist_mine_and_label(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, K, iou_threshold, max_rows, max_classes,
+                        top_pro=MIST_TOP_PRO, thres=MIST_THRES, nms_iou=MIST_NMS_IOU, proposal_boxes=None):
+    """get_pgt_mist (roi_heads.py:910-1040, no SAM) + label_and_sample_proposals_wsl's matching (:1722-1825) on the
+    device: select, merge, nms_segments (mask + scan), label -- five launches, no host read.  max_rows (the longest image)
+    and max_classes (the longest image-level class list) are HOST ints: they size the storage, k_cap = mist_k(max_rows)
+    lists rows per class slot.  boxes: what is mined (a later head's: the previous head's predictions); proposal_boxes: what
+    is labelled against the targets, the proposals themselves as in the reference (:1770-1772); None: `boxes`.  Returns
+    mist_label's dict."""
+    k_cap = mist_k(max_rows, top_pro)
+    if k_cap > MIST_K_CAP_MAX:  # (wsovod_mist_select refuses it too: WSOVOD_ERR_UNSUPPORTED)
+        raise RuntimeError(f"wsovod_hip mist_mine_and_label: k_cap = {k_cap} candidates per class (an image of {int(max_rows)} "
+                           f"proposals) is above the {MIST_K_CAP_MAX} pairs one workgroup of wsovod_mist_select sorts")
+    worst = int(max_classes) * k_cap
+    if worst > NMS_SEGMENT_MAX:
+        raise RuntimeError(f"wsovod_hip mist_mine_and_label: {int(max_classes)} image-level classes x {k_cap} candidates per "
+                           f"class = {worst} candidates in one image, wsovod_nms_segments holds {NMS_SEGMENT_MAX} boxes per "
+                           "segment")
+    boxes = boxes.to(torch.float32).contiguous()
+    sel = mist_select(scores, boxes, seg_offsets, gt_classes_img, gt_offsets, K, k_cap, top_pro, thres)
+    cand = mist_merge(*sel, boxes, seg_offsets, gt_classes_img, gt_offsets, max_classes)
+    keep_idx, keep_count = nms_segments(cand["boxes"], cand["seg"], worst, nms_iou, valid=cand["valid"])
+    if proposal_boxes is not None:
+        assert proposal_boxes.shape == boxes.shape
+        proposal_boxes = proposal_boxes.to(torch.float32).contiguous()
+    return mist_label(boxes if proposal_boxes is None else proposal_boxes, seg_offsets, gt_offsets, max_rows, cand, keep_idx,
+                      keep_count, K, iou_threshold)
+
+
 def subsample_labels(labels, keys, seg_offsets, max_rows, num_samples, positive_fraction, bg_label):
     """detectron2 subsample_labels on the device for every image at once (include/wsovod_hip.h): rows that are not
     sampled come back as -1.  `keys` (float32, one per row) order the rows inside their group."""

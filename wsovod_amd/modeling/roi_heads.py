@@ -9,9 +9,11 @@ append_background=True, file_names=None, loaded_proposals=None)` and return valu
 
 What is on the HIP path: RoI pooling with the fused objectness scale, the neck, object mining,
 pseudo-GT mining + proposal labelling (one kernel, no host syncs, replacing the python list
-comprehensions of get_pgt_top_k :1043-1343 and label_and_sample_proposals_wsl :1722-1825) and the
-instance-refinement branch.  Out of scope (raise): MIST
-refinement, in-loop SAM box refinement, `_vis_*` debug dumps.
+comprehensions of get_pgt_top_k :1043-1343 and label_and_sample_proposals_wsl :1722-1825), MIST mining
+(WSOVOD.INSTANCE_REFINEMENT.REFINE_MIST, get_pgt_mist :910-1040: per-class top 15 %, score floor, class-agnostic NMS;
+hip_ops.mist_mine_and_label, a variable number of targets per image, no host syncs either) and the
+instance-refinement branch.  Out of scope (raise): in-loop SAM box refinement,
+TRAIN_ON_PRED_BOXES, `_vis_*` debug dumps.
 """
 import inspect
 import os
@@ -82,16 +84,20 @@ class ROIHeads(nn.Module):
 
 class PseudoTargets:
     """list[Instances] view of the mining kernel's output.  `packed` = (boxes (T,4), start (G) int32, count (G)
-    int32) on the device: image g owns rows [start[g], start[g] + count[g])."""
+    int32) on the device: image g owns rows [start[g], start[g] + count[g]).  The starts are the mining result's own
+    `pgt_start` where it has one (MIST: capacity-padded rows), else the image-level class offsets `gt_off` (top-1 mining:
+    one row per class)."""
 
     def __init__(self, mined, gt_off, image_sizes):
-        self._o, self._off, self._sizes, self._items = mined, gt_off, image_sizes, None
-        self.packed = (mined["pgt_boxes"], gt_off[:-1].contiguous(), mined["pgt_count"])
+        start = mined.get("pgt_start")
+        self._o, self._sizes, self._items = mined, image_sizes, None
+        self._start = start if start is not None else gt_off[:-1].contiguous()
+        self.packed = (mined["pgt_boxes"], self._start, mined["pgt_count"])
 
     def _materialise(self):
         if self._items is None:
             G = len(self._sizes)
-            host = torch.cat([self._o["pgt_count"], self._off]).tolist()
+            host = torch.cat([self._o["pgt_count"], self._start]).tolist()
             counts, offs = host[:G], host[G:]
             self._items = []
             for g, size in enumerate(self._sizes):
@@ -141,9 +147,11 @@ class WSOVODROIHeads(ROIHeads):
                  cls_agnostic_bbox_known: bool = False, pooler_type: str = "ROIPool", rpn_on: bool = False,
                  metadata: Dict = None, precision: str = "bf16", **kwargs):
         super().__init__(**kwargs)
-        if refine_mist or sam is not None or train_on_pred_boxes:
-            raise NotImplementedError("MIST refinement / in-loop SAM / TRAIN_ON_PRED_BOXES are outside the "
-                                      "hot path (SURVEY section 2, F7)")
+        if sam is not None:
+            raise NotImplementedError("in-loop SAM box refinement is outside the hot path (SURVEY section 2, F7)")
+        if train_on_pred_boxes:
+            raise NotImplementedError("MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES is outside the hot path (SURVEY section 2)")
+        self.refine_mist = bool(refine_mist)
         if mrrp_on and mrrp_fast:
             raise NotImplementedError("wsovod_amd: MODEL.MRRP.TEST_BRANCH_IDX != -1 with MODEL.MRRP.MRRP_ON: every shipped "
                                       "MRRP config runs all branches (-1)")
@@ -450,18 +458,30 @@ class WSOVODROIHeads(ROIHeads):
 
     @torch.no_grad()
     def mine_and_label(self, k, prev_pred_scores, prev_pred_boxes, proposals, seg, nums):
-        """get_pgt_top_k (top_k=1, no SAM) + label_and_sample_proposals_wsl fused in one kernel.
+        """get_pgt_top_k (top_k=1, no SAM) + label_and_sample_proposals_wsl fused in one kernel; with REFINE_MIST,
+        get_pgt_mist (roi_heads.py:910-1040) + the same labelling on the MIST kernels (hip_ops.mist_mine_and_label): a
+        variable number of targets per image in capacity-padded rows, o["pgt_start"] / o["pgt_count"] on the device.
 
-        Returns (targets: per-image Instances{gt_boxes, gt_classes, gt_scores, gt_weights} as the
-        reference builds at roi_heads.py:1316-1341, lazily sliced; proposals_k: per-image Instances with
-        gt_classes / gt_boxes / gt_scores / gt_weights per proposal)."""
+        Returns (o: the kernels' dict -- o["pgt_*"] the targets (o["pgt_index"]: the proposal's index inside its image, -1
+        for the dummy target), o["gt_*"] per proposal; proposals_k: per-image Instances with gt_classes / gt_boxes /
+        gt_scores / gt_weights per proposal).  PseudoTargets(o, ...) cuts the reference's per-image target Instances
+        (:1027-1038, :1316-1341) lazily."""
         if not self.sampling_on:
             raise NotImplementedError("WSOVOD.SAMPLING.SAMPLING_ON=False is not used by the WSR configs")
         m = self.proposal_matchers[k]
         assert len(m.thresholds) == 3 and m.labels == [0, 1], "hot path supports Matcher([thr], [0, 1])"
-        o = H.pgt_mine_and_label(prev_pred_scores.to(torch.float32), prev_pred_boxes, seg, self._gt_cat,
-                                 self._gt_off, self.pred_class_img_logits, self.num_classes, m.thresholds[1],
-                                 max_gt_per_image=self._gt_max)
+        if self.refine_mist:
+            if prev_pred_boxes.dim() != 2 or prev_pred_boxes.size(1) != 4:
+                raise NotImplementedError(f"REFINE_MIST: prediction boxes of shape {tuple(prev_pred_boxes.shape)} (one box per "
+                                          "class) are not supported, the mining takes class-agnostic (R, 4) boxes")
+            o = H.mist_mine_and_label(prev_pred_scores.to(torch.float32), prev_pred_boxes, seg, self._gt_cat, self._gt_off,
+                                      self.num_classes, m.thresholds[1], max_rows=max(nums),
+                                      max_classes=min(self._gt_max, self.num_classes),
+                                      proposal_boxes=self.boxes_cat(proposals))
+        else:
+            o = H.pgt_mine_and_label(prev_pred_scores.to(torch.float32), prev_pred_boxes, seg, self._gt_cat,
+                                     self._gt_off, self.pred_class_img_logits, self.num_classes, m.thresholds[1],
+                                     max_gt_per_image=self._gt_max)
         if max(nums) > self.batch_size_per_images[k] or self.positive_sample_fractions[k] < 1.0:
             # _sample_proposals_wsl (roi_heads.py:1597-1610): rows outside the random sample are ignored (-1); every
             # row stays in place, so the boxes / scores / weights above are untouched

@@ -12,15 +12,17 @@ _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs"
 
 
 def hot_path_cfg(depth=18, K=20, D=512, precision="bf16", pooler="ROIPool", device="cuda", weight_path=None,
-                 emb_seed=7, rpn=False, freeze_at=None, backbone="resnet", mrrp=False):
+                 emb_seed=7, rpn=False, freeze_at=None, backbone="resnet", mrrp=False, mist=False):
     """WSOVOD_WSR_{18,50}_DC5_1x in proposals-only mode: the keys below are the values of
     /root/reference/configs/PascalVOC-Detection/{Base-RCNN-DilatedC5,WSOVOD_WSR_18_DC5_1x}.yaml
     that the hot path reads, with PROPOSAL_GENERATOR=PrecomputedProposals, BBOX_REFINE off.
     backbone="vgg16": WSOVOD_V_16_DC5_1x instead (hot_path_vgg16.yaml; `depth` is not read); with mrrp its MRRP form
     (hot_path_vgg16_mrrp.yaml: precomputed proposals only).  backbone="resnet" with mrrp: WSOVOD_MRRP_WSR_{18,50}_DC5_1x
     (hot_path_r{18,50}_mrrp.yaml: precomputed proposals only).  mrrp with rpn: the shipped form of those three, the MRRP RPN
-    next to the loaded proposals (hot_path_{vgg16,r18,r50}_mrrp_rpn.yaml, MODEL.HIP.MRRP_RPN on)."""
+    next to the loaded proposals (hot_path_{vgg16,r18,r50}_mrrp_rpn.yaml, MODEL.HIP.MRRP_RPN on).
+    mist: WSOVOD.INSTANCE_REFINEMENT.REFINE_MIST on top of the WSR_18 file (hot_path_r18_mist.yaml)."""
     cfg = get_cfg()
+    assert not mist or (backbone == "resnet" and not mrrp), "hot_path_r18_mist.yaml is the plain WSR_18 file + REFINE_MIST"
     if mrrp:
         assert backbone in ("vgg16", "resnet"), backbone
         name = ("hot_path_vgg16_mrrp" if backbone == "vgg16" else f"hot_path_r{depth}_mrrp") + ("_rpn.yaml" if rpn else ".yaml")
@@ -29,7 +31,9 @@ def hot_path_cfg(depth=18, K=20, D=512, precision="bf16", pooler="ROIPool", devi
         cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_vgg16_rpn.yaml" if rpn else "hot_path_vgg16.yaml"))
     else:
         assert backbone == "resnet", backbone
-        cfg.merge_from_file(os.path.join(_CONFIG_DIR, f"hot_path_wsr{depth}.yaml"))
+        if mist:
+            assert depth == 18
+        cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_r18_mist.yaml" if mist else f"hot_path_wsr{depth}.yaml"))
         if rpn:  # the shipped form: RPN boxes next to the loaded proposals
             assert depth == 18
             cfg.merge_from_file(os.path.join(_CONFIG_DIR, "hot_path_wsr18_rpn.yaml"))
@@ -134,6 +138,10 @@ def capture_full_step(model, batched_inputs, keep_grads_below=0):
     torch.cuda.synchronize()
     pgt = rh._last_pgt
     counts = pgt["pgt_count"].cpu().tolist()
+    pgt_boxes, pgt_classes = pgt["pgt_boxes"].cpu(), pgt["pgt_classes"].cpu()
+    if "pgt_start" in pgt:  # MIST mining: capacity-padded target rows, image g's at [pgt_start[g], + pgt_count[g])
+        rows = torch.cat([torch.arange(s, s + c) for s, c in zip(pgt["pgt_start"].cpu().tolist(), counts)])
+        pgt_boxes, pgt_classes = pgt_boxes[rows], pgt_classes[rows]
     out = {
         "losses": {k: float(v.detach()) for k, v in losses.items()},
         "mining_scores": captured["miner"][0].detach().float().cpu(),
@@ -141,7 +149,7 @@ def capture_full_step(model, batched_inputs, keep_grads_below=0):
         "refine_deltas": captured["refine"][1].detach().float().cpu(),
         "img_scores": rh.pred_class_img_logits.detach().float().cpu(),
         "gt_classes": pgt["gt_classes"].cpu(), "gt_boxes": pgt["gt_boxes"].cpu(), "gt_weights": pgt["gt_weights"].cpu(),
-        "pgt_num": counts, "pgt_boxes": pgt["pgt_boxes"].cpu(), "pgt_classes": pgt["pgt_classes"].cpu(),
+        "pgt_num": counts, "pgt_boxes": pgt_boxes, "pgt_classes": pgt_classes,
         # fp64 accumulation: an fp32 norm over fc1's 103 M elements is itself off by ~0.5 %
         "grad_norms": {k: float(p.grad.detach().double().norm()) for k, p in model.named_parameters()
                        if p.requires_grad and p.grad is not None},

@@ -705,7 +705,9 @@ class _GapNHWC(Function):
     @once_differentiable
     def backward(ctx, dy):
         n, h, w, c = ctx.shape
-        return (dy.to(torch.float32) / float(h * w)).view(n, 1, 1, c).expand(n, h, w, c).to(ctx.dtype)
+        # (a tensor divisor: by a Python scalar torch multiplies with the rounded reciprocal, two roundings instead of one)
+        count = H.const_tensor((float(h * w),), torch.float32, dy.device)
+        return (dy.to(torch.float32) / count).view(n, 1, 1, c).expand(n, h, w, c).to(ctx.dtype)
 
 
 def global_avgpool_nhwc(x):

@@ -690,6 +690,57 @@ int wsovod_mist_label(const float* boxes, const int* seg_offsets, int G, int max
                       float* pgt_weights, int* pgt_index, int* pgt_count, long long* out_classes, float* out_boxes,
                       float* out_scores, float* out_weights, int* out_matched, wsovod_stream_t stream);
 
+/* Test-time augmentation on the device (MODEL.HIP.TTA_DEVICE; test_time_augmentation_avg.py:67-334 and
+ * test_time_augmentation_union.py): the views of an image and the merge of their predictions without a host round trip.
+ *
+ * wsovod_resample_u8.  PIL.Image.resize((nw, nh), BILINEAR) of a uint8 plane-major (3, H, W) image, byte for byte (what
+ * detectron2's ResizeTransform does for uint8 images): Pillow's separable 22-bit fixed-point filter, horizontal pass first
+ * into the uint8 workspace tmp (3, H, nw), vertical pass from there.  out is (2, 3, nh, nw) with flip != 0 -- slice 0 the
+ * resized view, slice 1 its horizontal mirror, written by the same vertical launch -- and (1, 3, nh, nw) otherwise.
+ *   Per axis the host supplies Pillow's coefficient table, built in fp64: kk (n_out, ksize) int32 weights scaled by 2^22
+ *   and bounds (n_out, 2) int32 = (first tap, number of taps <= ksize); an output sample is
+ *   clamp((2^21 + sum pixel * k) >> 22, 0, 255).  An axis that keeps its size takes NULL tables and is copied; tmp may be
+ *   NULL when the width is kept.  tmp / out 4-byte aligned.
+ * There is no cap on ksize (taps are a loop over the table row).  A tensor or table of 2^31 bytes / entries or more is
+ * refused with WSOVOD_ERR_UNSUPPORTED; nothing is ever approximated. */
+int wsovod_resample_u8(const unsigned char* src, int H, int W, int nh, int nw, const int* kk_h, const int* bounds_h,
+                       int ksize_h, const int* kk_v, const int* bounds_v, int ksize_v, unsigned char* tmp,
+                       unsigned char* out, int flip, wsovod_stream_t stream);
+
+/* A view's way back to the original frame, TransformList.inverse().apply_box in float32 operation by operation: per corner
+ * x = flip_w - x (flip != 0 only; flip_w = the view's width), x *= sx, y *= sy (sx = float32(w_in / nw), sy =
+ * float32(h_in / nh), rounded on the host), x *= px, y *= py (has_pre != 0 only: the inverse of the mapper's pre-resize),
+ * then min / max over the corners.  No operation is contracted with another. */
+typedef struct {
+  int flip;
+  float flip_w;
+  float sx, sy;
+  int has_pre;
+  float px, py;
+} wsovod_tta_xform;
+
+#define WSOVOD_TTA_MAX_VIEWS 32
+typedef struct {
+  const float* boxes;  /* (R, box_cols) of this view */
+  const float* scores; /* (R, score_cols) of this view */
+  wsovod_tta_xform xf;
+} wsovod_tta_view;
+typedef struct {
+  int n_views;
+  wsovod_tta_view v[WSOVOD_TTA_MAX_VIEWS];
+} wsovod_tta_views;
+
+/* boxes (M, 4) -> out (M, 4) mapped by *xform (a host pointer, read before the call returns).  16-byte aligned. */
+int wsovod_tta_map_boxes(const float* boxes, int M, const wsovod_tta_xform* xform, float* out, wsovod_stream_t stream);
+
+/* GeneralizedRCNNWithTTAAVG's merge input in one launch: mean_boxes (R, box_cols) = the mean over the views of the
+ * back-mapped boxes (box_cols a multiple of 4), mean_scores (R, score_cols) = the mean of the scores.  Per element the
+ * views' float32 values are added in view order in fp64, divided by the view count in fp64 and rounded once to float32.
+ * *views is a host pointer to the table (passed to the kernel by value); more than WSOVOD_TTA_MAX_VIEWS views are refused
+ * with WSOVOD_ERR_UNSUPPORTED.  Box pointers 16-byte aligned. */
+int wsovod_tta_avg(const wsovod_tta_views* views, int R, int box_cols, int score_cols, float* mean_boxes,
+                   float* mean_scores, wsovod_stream_t stream);
+
 /* Proposal sub-sampling for the refinement losses, no grad.  Replaces detectron2 `subsample_labels` as called by
  * WSOVODROIHeads._sample_proposals_wsl (roi_heads.py:1566-1603) when an image has more proposals than
  * WSOVOD.SAMPLING.BATCH_SIZE_PER_IMAGE or POSITIVE_FRACTION < 1 (the shipped RPN configs: up to 4000 loaded + 1024

@@ -51,6 +51,25 @@ class ConvBranches(C.Structure):
     _fields_ = [("n_branch", C.c_int), ("dil", C.c_int * 4), ("pad", C.c_int * 4), ("shared_input", C.c_int)]
 
 
+TTA_MAX_VIEWS = 32  # WSOVOD_TTA_MAX_VIEWS
+
+
+class TtaXform(C.Structure):
+    """wsovod_tta_xform (include/wsovod_hip.h)."""
+    _fields_ = [("flip", C.c_int), ("flip_w", C.c_float), ("sx", C.c_float), ("sy", C.c_float),
+                ("has_pre", C.c_int), ("px", C.c_float), ("py", C.c_float)]
+
+
+class TtaView(C.Structure):
+    """wsovod_tta_view (include/wsovod_hip.h)."""
+    _fields_ = [("boxes", C.c_void_p), ("scores", C.c_void_p), ("xf", TtaXform)]
+
+
+class TtaViews(C.Structure):
+    """wsovod_tta_views (include/wsovod_hip.h)."""
+    _fields_ = [("n_views", C.c_int), ("v", TtaView * TTA_MAX_VIEWS)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_longlong), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -146,6 +165,9 @@ SIGNATURES = {
     "wsovod_mist_select": [_P, _L, _P, _P, _I, _P, _P, _I, _I, C.c_double, _F, _I, _P, _P, _P, _P],
     "wsovod_mist_merge": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "wsovod_mist_label": [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _F] + [_P] * 11 + [_P],
+    "wsovod_resample_u8": [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P],
+    "wsovod_tta_map_boxes": [_P, _I, C.POINTER(TtaXform), _P, _P],
+    "wsovod_tta_avg": [C.POINTER(TtaViews), _I, _I, _I, _P, _P, _P],
 }
 
 class SgdTensor(C.Structure):

@@ -250,6 +250,9 @@ def add_wsovod_config(cfg):
     # build WSOVODRPN_V2 with MODEL.MRRP.MRRP_ON (per-level anchors, grouped top-k, level ids).  Off by
     # default only because configs without the key are pinned to the earlier refusal
     _C.MODEL.HIP.MRRP_RPN = False
+    # test-time augmentation with the views built (Pillow-exact resample + mirror) and merged (back-mapping, AVG mean) on the
+    # device instead of PIL / numpy on the host (modeling/tta_device.py).  Opt-in
+    _C.MODEL.HIP.TTA_DEVICE = False
     return _C
 
 

@@ -1722,3 +1722,97 @@ def sum_shards_bf16(src, n_shards, dst):
         raise RuntimeError("sum_shards_bf16: contiguous bf16 src of n_shards * dst.numel() elements expected")
     check(lib().wsovod_sum_shards_bf16(src.data_ptr(), n_shards, dst.numel(), dst.data_ptr(), stream()), "sum_shards_bf16")
     return dst
+
+
+class Unsupported(RuntimeError):
+    """A kernel refused a shape it does not compute (WSOVOD_ERR_UNSUPPORTED): the caller may take its other route."""
+
+
+def _check_unsupported(rc, what):
+    if rc == 3:
+        raise Unsupported(f"wsovod_hip {what}: {lib().wsovod_last_error().decode(errors='replace')}")
+    check(rc, what)
+
+
+TTA_MAX_VIEWS = _lib.TTA_MAX_VIEWS  # views one wsovod_tta_avg launch takes
+_RESAMPLE_TABLES = {}
+
+
+def _resample_table_dev(n_in, n_out, device):
+    """pil_resample.resample_table on the device: (kk, bounds, ksize), uploaded once per (n_in, n_out) pair."""
+    key = (int(n_in), int(n_out), str(device))
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is None:
+        from .pil_resample import resample_table
+
+        kk, bounds, ksize = resample_table(n_in, n_out)
+        if len(_RESAMPLE_TABLES) > 256:
+            _RESAMPLE_TABLES.clear()
+        hit = _RESAMPLE_TABLES[key] = (torch.from_numpy(kk).to(device), torch.from_numpy(bounds).to(device), ksize)
+    return hit
+
+
+def resample_u8(img_chw_u8, nh, nw, flip=True):
+    """PIL.Image.resize((nw, nh), BILINEAR) of a uint8 (3, H, W) device image, byte for byte: (2, 3, nh, nw) -- the view
+    and its horizontal mirror, adjacent slices of one allocation -- or (1, 3, nh, nw) with flip=False.  Raises
+    `Unsupported` for a size the kernel refuses."""
+    require_gpu(img_chw_u8)
+    if img_chw_u8.dtype != torch.uint8 or img_chw_u8.dim() != 3 or img_chw_u8.shape[0] != 3:
+        raise RuntimeError(f"resample_u8: a uint8 (3, H, W) image expected, got {img_chw_u8.dtype} {tuple(img_chw_u8.shape)}")
+    img = img_chw_u8.contiguous()
+    dev, (_, Hh, Ww), nh, nw = img.device, img.shape, int(nh), int(nw)
+    if nh <= 0 or nw <= 0 or Hh == 0 or Ww == 0:
+        raise RuntimeError(f"resample_u8: empty size {Hh} x {Ww} -> {nh} x {nw}")
+    kh, bh, ksh = _resample_table_dev(Ww, nw, dev) if nw != Ww else (None, None, 0)
+    kv, bv, ksv = _resample_table_dev(Hh, nh, dev) if nh != Hh else (None, None, 0)
+    tmp = torch.empty((3, Hh, nw), dtype=torch.uint8, device=dev) if nw != Ww else None
+    out = torch.empty((2 if flip else 1, 3, nh, nw), dtype=torch.uint8, device=dev)
+    _check_unsupported(lib().wsovod_resample_u8(ptr(img), Hh, Ww, nh, nw, ptr(kh), ptr(bh), ksh, ptr(kv), ptr(bv), ksv,
+                                                ptr(tmp), ptr(out), 1 if flip else 0, stream()), "resample_u8")
+    return out
+
+
+def tta_xform(flip, flip_w, sx, sy, pre=None):
+    """wsovod_tta_xform of one view: un-flip about flip_w, scale by (sx, sy), then by pre = (px, py) when the mapper
+    resized the image before the views.  The factors are the float32 values numpy multiplies by."""
+    f32 = lambda v: C.c_float(v).value  # noqa: E731 -- the double rounded to float32, as numpy rounds a Python scalar
+    px, py = pre if pre is not None else (1.0, 1.0)
+    return _lib.TtaXform(1 if flip else 0, f32(flip_w), f32(sx), f32(sy), 0 if pre is None else 1, f32(px), f32(py))
+
+
+def tta_map_boxes(boxes, xform):
+    """boxes (M, 4) f32 of a view -> the original frame (TransformList.inverse().apply_box in float32, bit for bit)."""
+    require_gpu(boxes)
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise RuntimeError(f"tta_map_boxes: float32 (M, 4) boxes expected, got {boxes.dtype} {tuple(boxes.shape)}")
+    boxes = boxes.contiguous()
+    out = torch.empty_like(boxes)
+    check(lib().wsovod_tta_map_boxes(ptr(boxes), boxes.shape[0], C.byref(xform), ptr(out), stream()), "tta_map_boxes")
+    return out
+
+
+def tta_avg(view_boxes, view_scores, xforms):
+    """The AVG merge input: per view v, boxes (R, 4C) in the view's frame and scores (R, K+1); returns (mean of the
+    back-mapped boxes, mean of the scores), fp64 sums in view order rounded once.  More than 32 views raise `Unsupported`."""
+    V = len(view_boxes)
+    if V == 0 or len(view_scores) != V or len(xforms) != V:
+        raise RuntimeError("tta_avg: one box tensor, one score tensor and one transform per view, at least one view")
+    if V > _lib.TTA_MAX_VIEWS:
+        raise Unsupported(f"tta_avg: {V} views, one launch takes {_lib.TTA_MAX_VIEWS}")
+    require_gpu(*view_boxes, *view_scores)
+    R, bc, sc = view_boxes[0].shape[0], view_boxes[0].shape[1], view_scores[0].shape[1]
+    table = _lib.TtaViews()
+    table.n_views = V
+    keep = []
+    for v, (b, s, xf) in enumerate(zip(view_boxes, view_scores, xforms)):
+        if b.dtype != torch.float32 or s.dtype != torch.float32 or tuple(b.shape) != (R, bc) or tuple(s.shape) != (R, sc):
+            raise RuntimeError(f"tta_avg: view {v}: float32 ({R}, {bc}) boxes and ({R}, {sc}) scores expected, got "
+                               f"{b.dtype} {tuple(b.shape)} / {s.dtype} {tuple(s.shape)}")
+        b, s = b.contiguous(), s.contiguous()
+        keep.append((b, s))
+        table.v[v].boxes, table.v[v].scores, table.v[v].xf = b.data_ptr(), s.data_ptr(), xf
+    dev = view_boxes[0].device
+    mean_boxes = torch.empty((R, bc), dtype=torch.float32, device=dev)
+    mean_scores = torch.empty((R, sc), dtype=torch.float32, device=dev)
+    _check_unsupported(lib().wsovod_tta_avg(C.byref(table), R, bc, sc, ptr(mean_boxes), ptr(mean_scores), stream()), "tta_avg")
+    return mean_boxes, mean_scores

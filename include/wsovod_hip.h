@@ -741,6 +741,80 @@ int wsovod_tta_map_boxes(const float* boxes, int M, const wsovod_tta_xform* xfor
 int wsovod_tta_avg(const wsovod_tta_views* views, int R, int box_cols, int score_cols, float* mean_boxes,
                    float* mean_scores, wsovod_stream_t stream);
 
+/* Training input stage on the device (MODEL.HIP.INPUT_DEVICE; data/dataset_mapper.py:144-191 with detectron2's
+ * ResizeShortestEdge / RandomFlip and data/detection_utils.py:206-265): a batch of raw records becomes the model's
+ * `batched_inputs` without a per-image host pass.
+ *
+ * wsovod_resample_u8_batch.  PIL.Image.resize((nw, nh), BILINEAR) (what ResizeTransform.apply_image does for uint8 images)
+ * followed by HFlipTransform.apply_image and the zero padding of ImageList.from_tensors, for up to
+ * WSOVOD_INPUT_MAX_IMAGES images in TWO launches: one horizontal pass for the whole batch into `scratch`, one vertical pass
+ * that writes slot g of the uint8 canvas (n, 3, Hp, Wp) completely -- the image in [0, nh) x [0, nw), mirrored when the flip
+ * bit is set, zero everywhere else.  The arithmetic is wsovod_resample_u8's (Pillow's 22-bit fixed-point separable filter,
+ * horizontal pass first with a uint8 intermediate, no cap on ksize, nothing approximated; an axis that keeps its size is
+ * copied).  Per image:
+ *   src      device pointer to the uint8 source, plane-major (3, H, W) or, with WSOVOD_RESAMPLE_INTERLEAVED, (H, W, 3) as
+ *            detection_utils.read_image returns it;
+ *   kk_* / bounds_*  offsets (in int32 elements) into `tables` of the axis' Pillow coefficient table (kk (n_out, ksize),
+ *            bounds (n_out, 2), as for wsovod_resample_u8); ksize_* == 0 exactly when the axis keeps its size;
+ *   tmp      byte offset (a multiple of 4) into `scratch` of this image's (3, H, nw) intermediate, read only when the width
+ *            changes; the intermediates of a batch must not overlap.
+ * *batch is a host pointer (passed to the kernels by value, validated against table_ints / scratch_bytes / Hp / Wp before
+ * anything is launched).  canvas and scratch 4-byte aligned; canvas rows and slots need not be (Wp may be odd).  More than
+ * WSOVOD_INPUT_MAX_IMAGES images, or a tensor of 2^31 bytes or more, are refused with WSOVOD_ERR_UNSUPPORTED. */
+#define WSOVOD_INPUT_MAX_IMAGES 32
+#define WSOVOD_RESAMPLE_FLIP 1
+#define WSOVOD_RESAMPLE_INTERLEAVED 2
+typedef struct {
+  const unsigned char* src;
+  int H, W, nh, nw;
+  int flags; /* WSOVOD_RESAMPLE_FLIP | WSOVOD_RESAMPLE_INTERLEAVED */
+  int kk_h, bounds_h, ksize_h;
+  int kk_v, bounds_v, ksize_v;
+  int reserved;
+  long long tmp;
+} wsovod_resample_image;
+typedef struct {
+  int n;
+  wsovod_resample_image img[WSOVOD_INPUT_MAX_IMAGES];
+} wsovod_resample_batch;
+int wsovod_resample_u8_batch(const wsovod_resample_batch* batch, const int* tables, long long table_ints,
+                             unsigned char* scratch, long long scratch_bytes, unsigned char* canvas, int Hp, int Wp,
+                             wsovod_stream_t stream);
+
+/* wsovod_transform_proposals.  detection_utils.transform_proposals (:222-265) for up to WSOVOD_INPUT_MAX_IMAGES images in
+ * one call: image g owns rows [start, start + count) of boxes (total_rows, 4) float32 XYXY_ABS and logits (total_rows).
+ * Per box, the host's float32 operations one by one, none contracted:
+ *   1. TransformList.apply_box: per corner x *= sx, y *= sy (sx = float32(new_w / w), sy = float32(new_h / h), rounded on
+ *      the host), x = flip_w - x when flip != 0 (flip_w = float32(new_w)), then min / max over the corners;
+ *   2. Boxes.clip: x into [0, clip_w], y into [0, clip_h] (= new_w, new_h);
+ *   3. unique_boxes (:206-219): the first occurrence, in row order, of every distinct value of the hash
+ *      round_half_even(x1) + 1e3 round(y1) + 1e6 round(x2) + 1e9 round(y2), held as an int64 (equal to the host's fp64 value:
+ *      every term and partial sum is an integer below 2^53).  The key is the hash, not the box: different boxes with equal
+ *      hashes are duplicates, as on the host.  First occurrence = the minimum row per key, taken with atomics on an
+ *      open-addressed table in `workspace`, so the result does not depend on scheduling;
+ *   4. Boxes.nonempty(0): x2 - x1 > 0 and y2 - y1 > 0;
+ *   5. the first `topk` survivors, written densely with their logits to out_boxes (n, topk, 4) / out_logits (n, topk) at the
+ *      image's slot (rows past the count are zeroed) and their number to out_count (n) int32.
+ * The dedupe runs over the whole segment before the cut and no segment is staged in LDS: count is bounded by total_rows
+ * only.  Launches: one memset of the table and two kernels.  workspace: as many bytes as the _workspace_bytes query below
+ * returns for total_rows, 16-byte aligned like boxes / out_boxes.  Boxes must be finite (the host route asserts it).
+ * Refused with WSOVOD_ERR_UNSUPPORTED: more than WSOVOD_INPUT_MAX_IMAGES images; clip_w / clip_h that are not whole numbers
+ * in [1, 4e6] (above that the hash leaves the exact int64 / fp64 range). */
+typedef struct {
+  int start, count;
+  float sx, sy;
+  int flip;
+  float flip_w, clip_w, clip_h;
+} wsovod_proposal_image;
+typedef struct {
+  int n;
+  wsovod_proposal_image img[WSOVOD_INPUT_MAX_IMAGES];
+} wsovod_proposal_batch;
+long long wsovod_transform_proposals_workspace_bytes(int total_rows);
+int wsovod_transform_proposals(const wsovod_proposal_batch* batch, const float* boxes, const float* logits, int total_rows,
+                               int topk, void* workspace, long long workspace_bytes, float* out_boxes, float* out_logits,
+                               int* out_count, wsovod_stream_t stream);
+
 /* Proposal sub-sampling for the refinement losses, no grad.  Replaces detectron2 `subsample_labels` as called by
  * WSOVODROIHeads._sample_proposals_wsl (roi_heads.py:1566-1603) when an image has more proposals than
  * WSOVOD.SAMPLING.BATCH_SIZE_PER_IMAGE or POSITIVE_FRACTION < 1 (the shipped RPN configs: up to 4000 loaded + 1024

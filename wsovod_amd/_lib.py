@@ -70,6 +70,33 @@ class TtaViews(C.Structure):
     _fields_ = [("n_views", C.c_int), ("v", TtaView * TTA_MAX_VIEWS)]
 
 
+INPUT_MAX_IMAGES = 32  # WSOVOD_INPUT_MAX_IMAGES
+RESAMPLE_FLIP, RESAMPLE_INTERLEAVED = 1, 2  # wsovod_resample_image.flags
+
+
+class ResampleImage(C.Structure):
+    """wsovod_resample_image (include/wsovod_hip.h)."""
+    _fields_ = [("src", C.c_void_p)] + [(n, C.c_int) for n in (
+        "H", "W", "nh", "nw", "flags", "kk_h", "bounds_h", "ksize_h", "kk_v", "bounds_v", "ksize_v", "reserved")] + [
+        ("tmp", C.c_longlong)]
+
+
+class ResampleBatch(C.Structure):
+    """wsovod_resample_batch (include/wsovod_hip.h)."""
+    _fields_ = [("n", C.c_int), ("img", ResampleImage * INPUT_MAX_IMAGES)]
+
+
+class ProposalImage(C.Structure):
+    """wsovod_proposal_image (include/wsovod_hip.h)."""
+    _fields_ = [("start", C.c_int), ("count", C.c_int), ("sx", C.c_float), ("sy", C.c_float), ("flip", C.c_int),
+                ("flip_w", C.c_float), ("clip_w", C.c_float), ("clip_h", C.c_float)]
+
+
+class ProposalBatch(C.Structure):
+    """wsovod_proposal_batch (include/wsovod_hip.h)."""
+    _fields_ = [("n", C.c_int), ("img", ProposalImage * INPUT_MAX_IMAGES)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_longlong), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -168,6 +195,9 @@ SIGNATURES = {
     "wsovod_resample_u8": [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P],
     "wsovod_tta_map_boxes": [_P, _I, C.POINTER(TtaXform), _P, _P],
     "wsovod_tta_avg": [C.POINTER(TtaViews), _I, _I, _I, _P, _P, _P],
+    "wsovod_resample_u8_batch": [C.POINTER(ResampleBatch), _P, _L, _P, _L, _P, _I, _I, _P],
+    "wsovod_transform_proposals_workspace_bytes": [_I],
+    "wsovod_transform_proposals": [C.POINTER(ProposalBatch), _P, _P, _I, _I, _P, _L, _P, _P, _P, _P],
 }
 
 class SgdTensor(C.Structure):
@@ -210,7 +240,7 @@ def lib():
             fn.restype = C.c_int
         _lib.wsovod_last_error.restype = C.c_char_p
         for name in ("wsovod_colsum_workspace_floats", "wsovod_grad_clip_workspace_floats", "wsovod_roi_pool_workspace_bytes",
-                     "wsovod_max2x2_gap_workspace_floats"):
+                     "wsovod_max2x2_gap_workspace_floats", "wsovod_transform_proposals_workspace_bytes"):
             getattr(_lib, name).restype = C.c_longlong
         got = _lib.wsovod_abi_version()
         if got != ABI_VERSION:  # the structs of include/wsovod_hip.h (gemm desc, sgd tensor) changed size across versions

@@ -90,6 +90,8 @@ def _d2_defaults():
     _C.INPUT.FORMAT = "BGR"
     _C.INPUT.MIN_SIZE_TRAIN = (800,)
     _C.INPUT.MAX_SIZE_TRAIN = 1333
+    _C.INPUT.MIN_SIZE_TRAIN_SAMPLING = "choice"  # | "range": MIN_SIZE_TRAIN is then (min, max)
+    _C.INPUT.RANDOM_FLIP = "horizontal"  # | "none" (detectron2's "vertical" is not built here)
     _C.INPUT.MIN_SIZE_TEST = 800
     _C.INPUT.MAX_SIZE_TEST = 1333
     _C.INPUT.CROP = C({"ENABLED": False})
@@ -253,6 +255,9 @@ def add_wsovod_config(cfg):
     # test-time augmentation with the views built (Pillow-exact resample + mirror) and merged (back-mapping, AVG mean) on the
     # device instead of PIL / numpy on the host (modeling/tta_device.py).  Opt-in
     _C.MODEL.HIP.TTA_DEVICE = False
+    # training input stage (ResizeShortestEdge, RandomFlip, transform_proposals, zero padding) for the whole batch on the device
+    # instead of PIL / numpy per image on the host (data/train_input.py).  Opt-in
+    _C.MODEL.HIP.INPUT_DEVICE = False
     return _C
 
 

@@ -1816,3 +1816,137 @@ def tta_avg(view_boxes, view_scores, xforms):
     mean_scores = torch.empty((R, sc), dtype=torch.float32, device=dev)
     _check_unsupported(lib().wsovod_tta_avg(C.byref(table), R, bc, sc, ptr(mean_boxes), ptr(mean_scores), stream()), "tta_avg")
     return mean_boxes, mean_scores
+
+
+INPUT_MAX_IMAGES = _lib.INPUT_MAX_IMAGES  # images one wsovod_resample_u8_batch / wsovod_transform_proposals call takes
+
+
+class _ResampleTablePool:
+    """pil_resample.resample_table of every (n_in, n_out) pair met, side by side in ONE int32 device tensor: the pool
+    wsovod_resample_u8_batch indexes by offset.  A pair is uploaded once; a full pool is replaced by a fresh one (kernels
+    already enqueued keep the old tensor's memory: the allocator is stream-ordered) and fills again."""
+
+    def __init__(self, device, ints=1 << 20):
+        self.device, self.buf, self.used, self.where = device, torch.empty((ints,), dtype=torch.int32, device=device), 0, {}
+
+    def reserve(self, pairs):
+        """{(n_in, n_out): (kk offset, bounds offset, ksize)} for `pairs`, all valid in self.buf after the call."""
+        import numpy as np
+
+        from .pil_resample import resample_table
+
+        pairs = sorted({(int(a), int(b)) for a, b in pairs})
+        host = {p: resample_table(*p) for p in pairs}
+        size = lambda p: host[p][0].size + host[p][1].size  # noqa: E731
+        missing = [p for p in pairs if p not in self.where]
+        if self.used + sum(size(p) for p in missing) > self.buf.numel():
+            total = sum(size(p) for p in pairs)
+            self.buf = torch.empty((max(self.buf.numel(), 2 * total),), dtype=torch.int32, device=self.device)
+            self.used, self.where, missing = 0, {}, pairs
+        if missing:
+            parts, at = [], self.used
+            for p in missing:
+                kk, bounds, ksize = host[p]
+                self.where[p] = (at, at + kk.size, ksize)
+                parts += [kk.ravel(), bounds.ravel()]
+                at += size(p)
+            self.buf[self.used:at].copy_(torch.from_numpy(np.concatenate(parts)))
+            self.used = at
+        return {p: self.where[p] for p in pairs}
+
+
+_TABLE_POOLS = {}
+
+
+def _table_pool(device):
+    pool = _TABLE_POOLS.get(str(device))
+    if pool is None:
+        pool = _TABLE_POOLS[str(device)] = _ResampleTablePool(device)
+    return pool
+
+
+def resample_u8_batch(images, sizes, flips, interleaved=False, out=None):
+    """The images of a training batch resized (PIL.Image.resize((nw, nh), BILINEAR), byte for byte), mirrored where flips[g]
+    and zero-padded into one uint8 canvas (G, 3, max nh, max nw): two launches per INPUT_MAX_IMAGES images.
+    images[g]: a contiguous uint8 device tensor, plane-major (3, H, W) or -- interleaved (one bool, or one per image) --
+    (H, W, 3); sizes[g] = (nh, nw).  out: a contiguous uint8 (G, 3, max nh, max nw) device tensor to write instead of a new
+    one (every byte of it is written).  Raises `Unsupported` for what the kernel refuses."""
+    G = len(images)
+    if G == 0 or len(sizes) != G or len(flips) != G:
+        raise RuntimeError("resample_u8_batch: one size and one flip per image, at least one image")
+    inter = [bool(interleaved)] * G if isinstance(interleaved, (bool, int)) else [bool(v) for v in interleaved]
+    require_gpu(*images)
+    dev = images[0].device
+    geo = []
+    for g, (im, il) in enumerate(zip(images, inter)):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2 if il else 0] != 3 or not im.is_contiguous() or im.numel() == 0:
+            raise RuntimeError(f"resample_u8_batch: image {g}: a contiguous uint8 {'(H, W, 3)' if il else '(3, H, W)'} tensor "
+                               f"expected, got {im.dtype} {tuple(im.shape)}")
+        Hh, Ww = (int(im.shape[0]), int(im.shape[1])) if il else (int(im.shape[1]), int(im.shape[2]))
+        nh, nw = int(sizes[g][0]), int(sizes[g][1])
+        if nh <= 0 or nw <= 0:
+            raise RuntimeError(f"resample_u8_batch: image {g}: empty size {nh} x {nw}")
+        geo.append((Hh, Ww, nh, nw))
+    Hp, Wp = max(q[2] for q in geo), max(q[3] for q in geo)
+    pool = _table_pool(dev)
+    where = pool.reserve([(Ww, nw) for _, Ww, _, nw in geo if Ww != nw] + [(Hh, nh) for Hh, _, nh, _ in geo if Hh != nh])
+    tables = pool.buf
+    canvas = torch.empty((G, 3, Hp, Wp), dtype=torch.uint8, device=dev) if out is None else out
+    if canvas.dtype != torch.uint8 or tuple(canvas.shape) != (G, 3, Hp, Wp) or not canvas.is_contiguous() or canvas.device != dev:
+        raise RuntimeError(f"resample_u8_batch: out must be a contiguous uint8 {(G, 3, Hp, Wp)} tensor on {dev}")
+    slot = 3 * Hp * Wp
+    for g0 in range(0, G, INPUT_MAX_IMAGES):  # (a multiple of 32 slots further the canvas is 4-byte aligned again)
+        n = min(INPUT_MAX_IMAGES, G - g0)
+        batch = _lib.ResampleBatch()
+        batch.n = n
+        at = 0
+        for j in range(n):
+            (Hh, Ww, nh, nw), d = geo[g0 + j], batch.img[j]
+            d.src, d.H, d.W, d.nh, d.nw = images[g0 + j].data_ptr(), Hh, Ww, nh, nw
+            d.flags = (_lib.RESAMPLE_FLIP if flips[g0 + j] else 0) | (_lib.RESAMPLE_INTERLEAVED if inter[g0 + j] else 0)
+            if Ww != nw:
+                d.kk_h, d.bounds_h, d.ksize_h = where[(Ww, nw)]
+                d.tmp = at
+                at += (3 * Hh * nw + 3) // 4 * 4
+            if Hh != nh:
+                d.kk_v, d.bounds_v, d.ksize_v = where[(Hh, nh)]
+        scratch = torch.empty((at,), dtype=torch.uint8, device=dev) if at else None
+        _check_unsupported(lib().wsovod_resample_u8_batch(C.byref(batch), ptr(tables), tables.numel(), ptr(scratch), at,
+                                                          C.c_void_p(canvas.data_ptr() + g0 * slot), Hp, Wp, stream()),
+                           "resample_u8_batch")
+    return canvas
+
+
+def transform_proposals(boxes, logits, segments, topk):
+    """data/proposals.py:transform_proposals for every image of a batch on the device, bit for bit.  boxes (N, 4) float32
+    XYXY_ABS and logits (N,) float32 hold the images' rows back to back; segments[g] = (start, count, h, w, new_h, new_w,
+    flip).  Returns (out_boxes (G, topk, 4), out_logits (G, topk), counts (G,) int32): image g's survivors are
+    out_boxes[g, :counts[g]], the rows behind them zero.  Raises `Unsupported` for what the kernel refuses."""
+    require_gpu(boxes, logits)
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 4 or logits.dtype != torch.float32 \
+            or logits.dim() != 1 or logits.shape[0] != boxes.shape[0]:
+        raise RuntimeError(f"transform_proposals: float32 (N, 4) boxes and (N,) logits expected, got {boxes.dtype} "
+                           f"{tuple(boxes.shape)} / {logits.dtype} {tuple(logits.shape)}")
+    G, N, topk, dev = len(segments), int(boxes.shape[0]), int(topk), boxes.device
+    if G == 0 or topk < 1:
+        raise RuntimeError("transform_proposals: at least one image and topk >= 1")
+    boxes, logits = boxes.contiguous(), logits.contiguous()
+    f32 = lambda v: C.c_float(v).value  # noqa: E731 -- the double rounded to float32, as numpy rounds a Python scalar
+    out_boxes = torch.empty((G, topk, 4), dtype=torch.float32, device=dev)
+    out_logits = torch.empty((G, topk), dtype=torch.float32, device=dev)
+    counts = torch.empty((G,), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().wsovod_transform_proposals_workspace_bytes(N))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    for g0 in range(0, G, INPUT_MAX_IMAGES):
+        n = min(INPUT_MAX_IMAGES, G - g0)
+        batch = _lib.ProposalBatch()
+        batch.n = n
+        for j in range(n):
+            start, count, h, w, nh, nw, flip = segments[g0 + j]
+            d = batch.img[j]
+            d.start, d.count, d.sx, d.sy = int(start), int(count), f32(nw * 1.0 / w), f32(nh * 1.0 / h)
+            d.flip, d.flip_w, d.clip_w, d.clip_h = 1 if flip else 0, f32(nw), f32(nw), f32(nh)
+        _check_unsupported(lib().wsovod_transform_proposals(
+            C.byref(batch), ptr(boxes), ptr(logits), N, topk, ptr(ws), ws_bytes, ptr(out_boxes[g0]), ptr(out_logits[g0]),
+            ptr(counts[g0:]), stream()), "transform_proposals")
+    return out_boxes, out_logits, counts

@@ -108,7 +108,10 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         images = [x["image"] for x in batched_inputs]
         sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
         Hp, Wp = max(s[0] for s in sizes), max(s[1] for s in sizes)
-        if all(im.device == self.device for im in images) and all(s == sizes[0] for s in sizes):
+        canvas = self._padded_views(images, sizes, Hp, Wp, self.device)
+        if canvas is not None:
+            pass  # the device input stage's batch (data/train_input.py): already one zero-padded canvas, no pass at all
+        elif all(im.device == self.device for im in images) and all(s == sizes[0] for s in sizes):
             canvas = self._adjacent(images)  # already resident as consecutive slices of one batch tensor: no pass at all
             if canvas is None:
                 canvas = torch.stack(images)  # already resident: one gather pass
@@ -143,6 +146,22 @@ class GeneralizedRCNN_WSOVOD(nn.Module):
         if im0.storage_offset() + len(images) * n > st.nbytes() // esz:
             return None
         return im0.as_strided((len(images),) + tuple(im0.shape), (n,) + tuple(im0.stride()), im0.storage_offset())
+
+    @staticmethod
+    def _padded_views(images, sizes, Hp, Wp, device):
+        """The (N,3,Hp,Wp) canvas itself when `images` are the views canvas[i, :, :h_i, :w_i], i = 0..N-1, of ONE contiguous
+        uint8 canvas on `device` whose (Hp, Wp) are the batch maxima and whose producer marked it `zero_padded` (every byte
+        outside the views is 0: wsovod_resample_u8_batch writes whole slots), else None.  Checked by storage and strides."""
+        canvas = getattr(images[0], "_base", None)
+        if canvas is None or not getattr(canvas, "zero_padded", False) or canvas.device != device \
+                or canvas.dtype != torch.uint8 or tuple(canvas.shape) != (len(images), 3, Hp, Wp) or not canvas.is_contiguous():
+            return None
+        base, st, slot = canvas.data_ptr(), canvas.untyped_storage().data_ptr(), 3 * Hp * Wp
+        for i, (im, (h, w)) in enumerate(zip(images, sizes)):
+            if im.dtype != torch.uint8 or tuple(im.shape) != (3, h, w) or tuple(im.stride()) != (Hp * Wp, Wp, 1) \
+                    or im.data_ptr() != base + i * slot or im.untyped_storage().data_ptr() != st:
+                return None
+        return canvas
 
     def preprocess_image(self, batched_inputs):
         """rcnn_wsovod.py:321-328: normalise, pad and batch -> ImageList (fp32 NCHW)."""

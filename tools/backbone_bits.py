@@ -19,7 +19,16 @@ Cases (a 96 x 128 canvas, image sizes below the canvas so padding rows exist):
     grad/R18/freeze{0,2}/{bf16,fp32,parity}[/row_blocks]              weight gradients of sum(res5 * fixed_random); the
                                                                      input-side gradients of the later convs are inside those
                                                                      of the earlier ones
+    front/...                                                         hip_ops calls the backbones at this size do not reach,
+                                                                     each on the shape of the test that covers it: split-K
+                                                                     gemm_nt (bf16, bf16x2), the f16mx GEMM's split last
+                                                                     round, gemm_tn with every tile split / a split last
+                                                                     round, gemm_tn_sgd, mask_transpose with a column sum,
+                                                                     weighted_ce_forward
 "precision parity_mx": MX_MIN_TILES is lowered to 1 so that the crossing to the f16mx kernels happens at this size.
+
+--compare leaves out every entry whose digest differs between the two parent runs (a result that depends on atomics by
+design) and names it; none of the cases above is expected there outside stream capture.
 """
 import argparse
 import hashlib
@@ -144,6 +153,74 @@ class Cases:
             for precision in ("bf16", "fp32", "parity"):
                 yield f"grad/R18/freeze{freeze_at}/{precision}", self.grads(freeze_at, precision)
         yield "grad/R18/freeze0/parity/row_blocks", self.grads(0, "parity", 2048 * 9 * 64 * 4)
+        yield from self.fronts()
+
+    def fronts(self):
+        """The split / workspace paths of the GEMM fronts and their two neighbours (tests/test_gpu_gemm.py, test_gpu_f16mx.py,
+        test_gpu_head_kernels.py, test_gpu_fused_sgd.py name these shapes as the smallest at which each split engages)."""
+        from wsovod_amd.layers import hip_ops as H
+
+        gpu = self.gpu
+        rand = lambda seed, *shape: torch.rand(shape, generator=torch.Generator().manual_seed(seed)).to(gpu) - 0.5
+        randn = lambda seed, *shape: torch.randn(shape, generator=torch.Generator().manual_seed(seed)).to(gpu)
+
+        def split_k(x2):  # 3 x 5 tiles, K = 129 K-steps
+            def run():
+                M, N, K = 520, 1056 if x2 else 1032, 8192 + 64
+                a, b, bias = rand(1, M, K), rand(2, N, K), randn(3, N)
+                if x2:
+                    return {"c": H.gemm_nt(H.x2_encode(a), H.x2_encode(b), x2=True, out_dtype=torch.float32, bias=bias, relu=True)}
+                kw = dict(bias=bias, relu=True, residual=randn(4, M, N).to(torch.bfloat16), alpha=0.5, dropout_p=0.5, dropout_seed=77)
+                return {"c": H.gemm_nt(a.to(torch.bfloat16), b.to(torch.bfloat16), out_dtype=torch.float32, **kw)}
+            return run
+
+        def mx_tail():  # CUs + 18 row tiles: the last round's 18 tiles as K slices
+            cus = torch.cuda.get_device_properties(0).multi_processor_count
+            M, N, K = (cus + 18) * 256 - 100, 256, 1536
+            A, _ = H.mx_encode(torch.relu(randn(5, M, K)), unit=True)
+            B, sb = H.mx_encode(randn(6, N, K) * 0.03)
+            return {"c": H.gemm_mx(A, None, B, sb, bias=randn(7, N), relu=True, dropout_p=0.5, dropout_seed=11)}
+
+        def tn(Mred, NI, NJ):
+            def run():
+                P, Q = rand(8, Mred, NI).to(torch.bfloat16), rand(9, Mred, NJ).to(torch.bfloat16)
+                old, H.DETERMINISTIC = H.DETERMINISTIC, False  # (the deterministic mode switches the split tail off)
+                try:
+                    return {"dw": H.gemm_tn(P, Q), "dw_acc": H.gemm_tn(P, Q, out=randn(10, NI, NJ), alpha=0.5, accumulate=True)}
+                finally:
+                    H.DETERMINISTIC = old
+            return run
+
+        def tn_sgd():  # 3 x 5 ragged tiles, two steps, the second with the rate in device memory
+            Mred, NI, NJ = 300, 520, 1056
+            dA, x = (randn(11, Mred, NI) * 0.1).to(torch.bfloat16), H.x2_encode(randn(12, Mred, NJ))
+            w, buf = randn(13, NI, NJ) * 0.05, torch.zeros(NI, NJ, device=gpu)
+            shadow = H.x2_encode(w)
+            H.gemm_tn_sgd(dA, x, w, buf, shadow, 0.013, 5e-4, 0.9, q_x2=True)
+            H.gemm_tn_sgd(dA, x, w, buf, shadow, torch.tensor([0.013], device=gpu), 5e-4, 0.9, q_x2=True)
+            return {"param": w, "momentum": buf, "shadow": shadow}
+
+        def colsum():
+            M, N = 8192, 1024
+            cs = torch.zeros(N, device=gpu)
+            dA, _ = H.mask_transpose(randn(14, M, N), randn(15, M, N), 0.5, torch.bfloat16, want_t=False, colsum=cs)
+            return {"dA": dA, "colsum": cs}
+
+        def ce():
+            M, K = 16384, 20
+            gt = torch.randint(-1, K + 1, (M,), generator=torch.Generator().manual_seed(17)).to(gpu)
+            w = torch.rand(M, generator=torch.Generator().manual_seed(18)).to(gpu)
+            loss, dlogits, accum = H.weighted_ce_forward(randn(16, M, K + 1) * 4, gt, w, True)
+            return {"loss": loss, "dlogits": dlogits, "accum": accum}
+
+        yield "front/gemm_nt_split_k/bf16", split_k(False)
+        yield "front/gemm_nt_split_k/bf16x2", split_k(True)
+        yield "front/gemm_mx_tail_split", mx_tail
+        yield "front/gemm_tn/every_tile_split", tn(16384, 512, 1024)  # 8 tiles x 8 slices
+        yield "front/gemm_tn/tail_split", tn(4096, 256 * 17, 256 * 16)  # 272 tiles = 256 + 16 split
+        yield "front/gemm_tn_sgd", tn_sgd
+        yield "front/mask_transpose_colsum", colsum
+        yield "front/weighted_ce_forward", ce
 
     def rpn_head_conv(self):
         from wsovod_amd.layers import hip_ops as H

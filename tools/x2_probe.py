@@ -63,7 +63,7 @@ def gemm_case(name, M, N, K, tiles):
 if __name__ == "__main__":
     conv_case("stem 64->64 300x400 (c64 halo vs generic)", 300, 400, 64, 64, 3, 1, [0, 1256064])
     conv_case("res2 64->64 150x200", 150, 200, 64, 64, 3, 1, [0, 1256064], residual=True)
-    if os.environ.get("X2_PROBE_C64_ONLY"):  # (WSOVOD_C64X_LEPI=0 / 1 in two processes: the switch is read once)
+    if os.environ.get("X2_PROBE_C64_ONLY"):  # (WSOVOD_C64X_LEPI=0 / 1 in two processes: one counter profile per setting)
         conv_case("stem 64->64 300x400 + 2x2 max pool", 300, 400, 64, 64, 3, 1, [0], pool=2)
         conv_case("res2 64->64 150x200, no residual", 150, 200, 64, 64, 3, 1, [0])
         sys.exit(0)

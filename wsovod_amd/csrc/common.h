@@ -8,13 +8,39 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/wsovod_hip.h"
+#include "scratch.h"
 
 namespace wsovod {
 
 void set_error(const char* fmt, ...);
+
+// The device API behind wsovod::Scratch (scratch.h; defined in runtime.hip): hipMalloc, hipStreamIsCapturing, hipGetDevice
+struct HipScratchApi {
+  typedef hipStream_t stream_t;
+  static void* alloc(size_t bytes);
+  static bool capturing(hipStream_t stream);
+  static int device();
+};
+typedef ScratchT<HipScratchApi> Scratch;
+
+// compute units of the current device (cached per device; 256 when the runtime cannot say)
+int cu_count();
+
+// Environment knobs, read at every call: "NAME=0" switches a default route off, "NAME=1" an experiment on
+inline bool env_is(const char* name, char c) {
+  const char* v = getenv(name);
+  return v && v[0] == c;
+}
+inline bool env_off(const char* name) { return env_is(name, '0'); }
+inline bool env_on(const char* name) { return env_is(name, '1'); }
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // Per-kernel profiling table (hipEvent bracketed launches; see runtime.hip).
 int prof_slot(const char* name);  // stable slot id for a kernel family name
@@ -62,6 +88,10 @@ int x2_add_group_rows(const void* x, long long ldx, const int* row_group, const 
       return WSOVOD_ERR_HIP;                                                                 \
     }                                                                                        \
   } while (0)
+
+// More than 64 KiB of dynamic LDS for `kernel` (parenthesise a template-id that has commas)
+#define WS_OPT_IN_LDS(kernel, bytes, what) \
+  WS_CHECK_HIP(hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)), what)
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

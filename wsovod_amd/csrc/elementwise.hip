@@ -6,7 +6,6 @@
 #include "f16mx.h"
 #include "gemm_common.h"
 #include <algorithm>
-#include <vector>
 
 namespace {
 
@@ -1106,26 +1105,12 @@ __global__ __launch_bounds__(256) void colsum_rows_kernel(const float* __restric
   }
 }
 
-// Workspace of the column-sum partials (single-stream use, as the rest of the library): never freed once handed out (a
-// captured HIP graph keeps its pointer), not grown under stream capture -- nullptr then, and the kernel falls back to atomics
+// Workspace of the column-sum partials (wsovod::Scratch, doubling): not grown under stream capture -- nullptr then, and the
+// kernel falls back to atomics
 float* colpart_workspace(size_t floats, hipStream_t s) {
-  static float* ws = nullptr;
-  static size_t ws_floats = 0;
-  static std::vector<float*> retired;
-  if (floats > ws_floats) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return nullptr;
-    const size_t want = std::max(floats, 2 * ws_floats);
-    float* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, want * sizeof(float)) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    if (ws) retired.push_back(ws);
-    ws = fresh;
-    ws_floats = want;
-  }
-  return ws;
+  static wsovod::Scratch ws(wsovod::ScratchGrowth::doubling());
+  wsovod::ScratchStatus st;
+  return (float*)ws.reserve(floats * sizeof(float), s, &st);
 }
 
 }  // namespace

@@ -1831,18 +1831,13 @@ int launch(const GemmArgs& a, hipStream_t s, const char* slot_name, double flops
   constexpr int lds_bytes = STAGES * (BM + BN) * 128;
   auto kfn = gemm_nt_kernel<T, BM, BN, CONV, WM, WN, DMA, STAGES, X3>;
   if (!attr_set) {
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt: LDS opt-in");
+    WS_OPT_IN_LDS(kfn, lds_bytes, "wsovod_gemm_nt: LDS opt-in");
     attr_set = true;
   }
   GemmArgs args = a;
   args.tiles_m = ceil_div(a.M - a.m_base, BM);
   args.tiles_n = ceil_div(a.N, BN);
-  {
-    const int run = std::max(1, args.tiles_m * args.tiles_n / 8);  // tiles per XCD
-    int g = 1;
-    while ((g + 1) * (g + 1) <= run) ++g;
-    args.group_m = std::max(1, std::min(g, args.tiles_m));
-  }
+  args.group_m = tile_group_height(args.tiles_m, args.tiles_n, INT_MAX);
   wsovod::ProfScope prof(slot, s, flops, bytes);
   hipLaunchKernelGGL(kfn, dim3(args.tiles_m * args.tiles_n), dim3(64 * WM * WN), lds_bytes, s, args);
   WS_CHECK_LAUNCH(slot_name);
@@ -2050,75 +2045,18 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
   WS_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "wsovod_gemm_nt: dropout_p must be in [0,1)");
   WS_CHECK_ARG(!d->group_add || d->row_group, "wsovod_gemm_nt: group_add needs row_group");
 
-  GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.A = (const char*)d->A;
-  a.B = (const char*)d->B;
   const bool planar = d->a_plane_bytes != 0;
   WS_CHECK_ARG(!planar || (x2 && !d->conv && d->a_plane_bytes > 0 && d->a_plane_bytes % 16 == 0 &&
                            d->a_plane_bytes + 256ll * d->lda * 2 < (1ll << 31) && d->lda % 8 == 0),
                "wsovod_gemm_nt: a_plane_bytes needs a bf16x2 plain GEMM, 16-byte aligned planes and planes + 256 rows < 2 GiB");
-  a.a_plane = d->a_plane_bytes;
-  a.lda = planar ? d->lda : d->lda * xs;  // (a plane row holds lda bf16 values; the interleaved row 2 * lda slots)
-  a.ldb = d->ldb * xs;
-  a.M = d->M;
-  a.N = d->N;
-  a.K = d->K * xs;
-  a.C = d->C;
-  a.ldc = d->ldc;
-  a.dtype_c = d->dtype_c;
-  a.Ct = d->Ct;
-  a.ldct = d->ldct;
-  a.dtype_ct = d->dtype_ct;
-  a.alpha = d->alpha;
-  a.row_scale = d->row_scale;
-  a.bias = d->bias;
-  a.residual = d->residual;
-  a.ldr = d->ldr;
-  a.dtype_r = d->dtype_r;
-  a.relu = d->relu;
-  a.dropout_p = d->dropout_p;
-  a.seed = d->dropout_seed;
-  a.seed_add = d->dropout_seed_add;
-  a.row_group = d->row_group;
-  a.group_add = d->group_add;
-  a.ld_ga = d->ld_ga;
-  a.mask_src = d->mask_src;
-  a.ldm = d->ldm;
-  a.dtype_m = d->dtype_m;
-  a.mask_scale = d->mask_scale;
-  a.accumulate = d->accumulate;
+  GemmArgs a;
+  fill_gemm_args(a, *d, xs);
 
   double bytes;
   if (d->conv) {
     const wsovod_conv_geom& g = d->geom;
     const int bke = d->dtype_in == WSOVOD_BF16 ? 64 : 32;  // values per K-step (bf16x2: 32 values = 64 bf16 slots)
-    WS_CHECK_ARG(g.Cin > 0 && g.Cin % bke == 0, "wsovod_gemm_nt(conv): Cin=%d must be a multiple of %d", g.Cin, bke);
-    WS_CHECK_ARG(!d->A2 || (d->Cin2 > 0 && d->Cin2 % bke == 0 && ((uintptr_t)d->A2 & 15) == 0),
-                 "wsovod_gemm_nt(conv): the fused shortcut input needs Cin2 (%d) a multiple of %d and 16-byte alignment", d->Cin2, bke);
-    WS_CHECK_ARG(d->K == g.KH * g.KW * g.Cin + (d->A2 ? d->Cin2 : 0), "wsovod_gemm_nt(conv): K=%d != KH*KW*Cin (+ Cin2)", d->K);
-    WS_CHECK_ARG(g.KH * g.KW <= 32, "wsovod_gemm_nt(conv): filters of more than 32 taps are not supported (per-tap validity mask)");
-    WS_CHECK_ARG((long long)d->M == (long long)g.n_img * g.Ho * g.Wo, "wsovod_gemm_nt(conv): M=%d != n_img*Ho*Wo", d->M);
-    WS_CHECK_ARG(g.stride >= 1 && g.dil >= 1 && g.pad >= 0, "wsovod_gemm_nt(conv): bad stride/dil/pad");
-    a.H = g.H;
-    a.W = g.W;
-    a.Cin = g.Cin * xs;
-    a.Ho = g.Ho;
-    a.Wo = g.Wo;
-    a.KH = g.KH;
-    a.KW = g.KW;
-    a.stride = g.stride;
-    a.pad = g.pad;
-    a.dil = g.dil;
-    a.pool = g.pool;
-    a.a_bytes = (long long)g.n_img * g.H * g.W * g.Cin * esz * xs;
-    if (d->A2) {
-      a.A2 = (const char*)d->A2;
-      a.Cin2 = d->Cin2 * xs;
-      a.a2_bytes = (long long)g.n_img * g.Ho * g.Wo * d->Cin2 * esz * xs;
-      WS_CHECK_ARG(a.a2_bytes < (1ll << 31), "wsovod_gemm_nt(conv): fused shortcut input exceeds the 2 GiB buffer-addressing limit");
-    }
-    WS_CHECK_ARG(a.a_bytes < (1ll << 31), "wsovod_gemm_nt(conv): input of %lld bytes exceeds the 2 GiB buffer-addressing limit", a.a_bytes);
+    if (int rc = check_and_fill_conv(a, *d, xs, esz, bke, /*border_in_limit=*/false, "wsovod_gemm_nt")) return rc;
     bytes = ((double)g.n_img * g.H * g.W * g.Cin + (double)d->N * d->K + (d->A2 ? (double)g.n_img * g.Ho * g.Wo * d->Cin2 : 0.0)) * esz * xs;
   } else {
     WS_CHECK_ARG(d->lda % (x2 ? 4 : epc) == 0, "wsovod_gemm_nt: lda=%lld must be a multiple of %d elements", d->lda, x2 ? 4 : epc);
@@ -2133,12 +2071,8 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
                "wsovod_gemm_nt: a bf16x2 residual needs N and ldr multiples of 32");
   const double flops = (x2 ? 6.0 : 2.0) * d->M * d->N * d->K;  // bf16x2: three bf16 MFMA products per value pair
   hipStream_t s = (hipStream_t)stream;
-  if (br) {  // the 2 GiB limit is kept for the WHOLE n_branch * N operand, with the largest branch's border in front
-    int pmax = 0;
-    for (int b = 0; b < br->n_branch; ++b) pmax = std::max(pmax, br->pad[b]);
-    WS_CHECK_ARG(a.a_bytes * (br->shared_input ? 1 : br->n_branch) + (long long)(pmax * a.W + pmax) * a.Cin * 2 < (1ll << 31) &&
-                     (long long)d->M * br->n_branch < (1ll << 31),
-                 "wsovod_gemm_conv_branches: the n_branch * N input exceeds the 2 GiB buffer-addressing limit");
+  if (br) {
+    if (int rc = check_branch_limit(a, *br, "wsovod_gemm_conv_branches")) return rc;
     const double wbytes = (double)d->N * d->K * 4.0;
     if (ex) {
       const double rbytes = d->residual ? (double)d->M * d->N * 4.0 * (*ex ? 1 : br->n_branch) : 0.0;
@@ -2161,17 +2095,16 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
     const int lds_bytes = C64_PATCH_BYTES + 2 * 8192;
     const int tiles_x = ceil_div(a.W, C64_TW), tiles_y = ceil_div(a.H, C64_TH);
     const int n_tiles = d->geom.n_img * tiles_x * tiles_y;
-    const char* pe = getenv("WSOVOD_C64_PERSIST");  // "0": always the one-tile kernel (A/B runs, tests)
-    const bool persist = !(pe && pe[0] == '0');
+    const bool persist = !wsovod::env_off("WSOVOD_C64_PERSIST");  // "0": always the one-tile kernel (A/B runs, tests)
     wsovod::ProfScope prof(slot, s, flops, bytes);
     if (persist && n_tiles >= 512) {  // enough tiles for two per CU: resident weights + double-buffered patches
       static bool attr = false;
       if (!attr) {
-        WS_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_c64p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, C64P_LDS_BYTES), "wsovod_gemm_nt: LDS opt-in");
-        WS_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_c64p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, C64P_LDS_BYTES), "wsovod_gemm_nt: LDS opt-in");
+        WS_OPT_IN_LDS(conv3x3_c64p_kernel<true>, C64P_LDS_BYTES, "wsovod_gemm_nt: LDS opt-in");
+        WS_OPT_IN_LDS(conv3x3_c64p_kernel<false>, C64P_LDS_BYTES, "wsovod_gemm_nt: LDS opt-in");
         attr = true;
       }
-      const char* wr = getenv("WSOVOD_C64_WREG");  // "0": weights read from LDS at every step (the round-2 form; A/B runs)
+      const bool wreg = !wsovod::env_off("WSOVOD_C64_WREG");  // "0": weights read from LDS at every step (the round-2 form; A/B runs)
       // the register-weights form: bf16 output, 16-byte aligned rows, buffer-addressable output / residual
       const bool lean = d->dtype_c == WSOVOD_BF16 && (d->ldc & 7) == 0 && ((uintptr_t)d->C & 15) == 0 &&
                         (!d->bias || ((uintptr_t)d->bias & 3) == 0) && (double)d->M * d->ldc * 2 < 2147483648.0 &&
@@ -2181,7 +2114,7 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
 #if (C64P_ABL & 64)
       if (const char* dp = getenv("WSOVOD_C64_DEBUG_PTR")) a.partial = (float*)strtoull(dp, nullptr, 16);
 #endif
-      if ((wr && wr[0] == '0') || !lean)
+      if (!wreg || !lean)
         hipLaunchKernelGGL(conv3x3_c64p_kernel<false>, dim3(256), dim3(256), C64P_LDS_BYTES, s, a, tiles_x, tiles_y, n_tiles);
       else
         hipLaunchKernelGGL(conv3x3_c64p_kernel<true>, dim3(256), dim3(256), C64P_LDS_BYTES, s, a, tiles_x, tiles_y, n_tiles);
@@ -2197,14 +2130,14 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
       a.pad == 1 && a.dil == 1 && a.Ho == a.H && a.Wo == a.W && d->C && d->dtype_c == WSOVOD_BF16X2 && !d->Ct && !d->A2 &&
       !d->row_scale && !d->group_add && !d->mask_src && !d->accumulate && d->dropout_p == 0.f && d->ldc % 32 == 0 &&
       (!d->residual || (d->dtype_r == WSOVOD_BF16X2 && d->ldr % 32 == 0)) && (a.pool == 0 || a.pool == 2) &&
-      !(getenv("WSOVOD_C64_X3") && getenv("WSOVOD_C64_X3")[0] == '0')) {
+      !wsovod::env_off("WSOVOD_C64_X3")) {
     static int slot = wsovod::prof_slot("conv3x3_c64_halo_bf16x2");
     static bool attr = false;
     if (!attr) {
-      WS_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_c64_x3_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, C64X<16>::LDS_BYTES), "wsovod_gemm_nt: LDS opt-in");
-      WS_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_c64_x3_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, C64X<32>::LDS_BYTES), "wsovod_gemm_nt: LDS opt-in");
-      WS_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_c64_x3h_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, C64XH::LDS_BYTES), "wsovod_gemm_nt: LDS opt-in");
-      WS_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_c64_x3h_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, C64XH::LDS_BYTES), "wsovod_gemm_nt: LDS opt-in");
+      WS_OPT_IN_LDS(conv3x3_c64_x3_kernel<16>, C64X<16>::LDS_BYTES, "wsovod_gemm_nt: LDS opt-in");
+      WS_OPT_IN_LDS(conv3x3_c64_x3_kernel<32>, C64X<32>::LDS_BYTES, "wsovod_gemm_nt: LDS opt-in");
+      WS_OPT_IN_LDS(conv3x3_c64_x3h_kernel<false>, C64XH::LDS_BYTES, "wsovod_gemm_nt: LDS opt-in");
+      WS_OPT_IN_LDS(conv3x3_c64_x3h_kernel<true>, C64XH::LDS_BYTES, "wsovod_gemm_nt: LDS opt-in");
       attr = true;
     }
     const char* tw = getenv("WSOVOD_C64X_TW");  // "16" / "32": the whole-K forms (A/B runs); default: the half-K 8 x 32 tile
@@ -2216,7 +2149,7 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
 #endif
     wsovod::ProfScope prof(slot, s, flops, bytes);
     // epilogue through LDS (whole-pixel stores): output rows of exactly one pixel's 256 B ("0": direct stores; A/B runs)
-    static const bool lepi_on = !(getenv("WSOVOD_C64X_LEPI") && getenv("WSOVOD_C64X_LEPI")[0] == '0');
+    const bool lepi_on = !wsovod::env_off("WSOVOD_C64X_LEPI");
     if (halfk && lepi_on && ((uintptr_t)d->C & 15) == 0 && d->ldc % 4 == 0)
       hipLaunchKernelGGL(conv3x3_c64_x3h_kernel<true>, dim3(n_tiles), dim3(256), C64XH::LDS_BYTES, s, a, tiles_x, tiles_y);
     else if (halfk)
@@ -2235,7 +2168,7 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
   // shapes, tools/gemm_ab.py); the implicit-GEMM conv stays on the 16-wavefront form (tools/conv_ab.py)
   // (round 5: in its lean two-phase form -- 1080 -> 1230, 705 -> 770, 1196 -> 1229 TFLOP/s against the four-phase form on
   // the dX shapes 16384 x 4096 x 4096 / x 1088 and 16384 x 25088 x 4096, bit-identical; tools/gemm_ab.py)
-  static const int bf16_tile = getenv("WSOVOD_BF16_TILE") ? atoi(getenv("WSOVOD_BF16_TILE")) : 2256256;
+  static const int bf16_tile = wsovod::env_int("WSOVOD_BF16_TILE", 2256256);
   if (!d->tile_hint && tile == 256256 && d->dtype_in == WSOVOD_BF16 && !d->conv) tile = bf16_tile;
   // few rows, long K (the FC layers at 1-4 images per step): the same tile with split-K instead of a small-tile grid
   // (measured, M = 512: K = 25088 230 -> 143 us; at K = 4096 the workspace round trip costs more than it saves: 40 -> 53 us)
@@ -2248,7 +2181,7 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
   // along N (256x128, still one workgroup per CU), fit ONE round, the rows behind the last full round go through a second
   // launch with that tile: ~0.6 of a tile time instead of 1.  Same products in the same order per output element.
   if (d->conv && !d->tile_hint && tile == 256256 && d->dtype_in != WSOVOD_F32 &&
-      !(getenv("WSOVOD_CONV_TAIL") && getenv("WSOVOD_CONV_TAIL")[0] == '0')) {
+      !wsovod::env_off("WSOVOD_CONV_TAIL")) {
     const int tm = ceil_div(d->M, 256), tn = ceil_div(d->N, 256);
     const long long tiles = (long long)tm * tn;
     const int rounds = (int)(tiles / 256);
@@ -2262,14 +2195,14 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
       at.m_base = main_tm * 256;
       // bf16x2: the main rounds on the lean two-phase 8-wavefront tile (round 5: 1331 / 1452 / 1384 against 1270 / 1366 /
       // 1315 TFLOP/s executed for the 16-wavefront tile on res4 / res5 / res5a, tools/conv_x2_ab.py; WSOVOD_CONV_8PH=0: A/B)
-      static const bool conv8 = !(getenv("WSOVOD_CONV_8PH") && getenv("WSOVOD_CONV_8PH")[0] == '0');
+      const bool conv8 = !wsovod::env_off("WSOVOD_CONV_8PH");
       int rc = x2 ? dispatch_tile_x3<true>(am, conv8 ? 2256256 : 256256, s, flops * fmain, bytes * fmain)
                   : dispatch_tile<bf16_t, true>(am, 256256, s, flops * fmain, bytes * fmain);
       if (rc != WSOVOD_OK) return rc;
       // round 5: a tail of few tiles and a long K (res5: 84 tiles, 72 K-steps) as split-K slices of the lean 8-wavefront
       // tile (3 x 84 workgroups of 24 K-steps + the finalize pass) instead of 168 half-width tiles of 72
       // (WSOVOD_CONV_TAIL_SPLITK=0: A/B runs; changes the summation order of the tail rows only)
-      const bool tail_split = !(getenv("WSOVOD_CONV_TAIL_SPLITK") && getenv("WSOVOD_CONV_TAIL_SPLITK")[0] == '0');
+      const bool tail_split = !wsovod::env_off("WSOVOD_CONV_TAIL_SPLITK");
       const int tail_t = ceil_div((int)tail_rows, 256) * tn, nk64 = ceil_div(d->K, 64);
       if (x2 && conv8 && tail_split && tail_t <= 128 && nk64 >= 32 && std::min(std::min(8, 256 / tail_t), nk64 / 16) >= 2)
         return dispatch_tile_x3<true>(at, 2256256, s, flops * (1.0 - fmain), bytes * (1.0 - fmain));
@@ -2281,8 +2214,7 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
     // plain contractions: the 8-wavefront tile in its two-phase form (48 MFMAs per phase; measured on the fc1 / fc2 /
     // projection shapes: 6.63 -> 6.14, 1.12 -> 1.03, 0.274 -> 0.263 ms against the four-phase form, tools/x2_probe.py);
     // the implicit-GEMM convs stay on the 16-wavefront tile (res5: 2.32 vs 2.40 ms)
-    if (!d->tile_hint && tile == 256256 &&
-        (!d->conv || !(getenv("WSOVOD_CONV_8PH") && getenv("WSOVOD_CONV_8PH")[0] == '0')))
+    if (!d->tile_hint && tile == 256256 && (!d->conv || !wsovod::env_off("WSOVOD_CONV_8PH")))
       tile = 2256256;  // (round 5: also the implicit-GEMM convs, in the lean form of that tile)
     // few rows, long K (fc1 at 1-4 images per step): the same tile with split-K, as for plain bf16 above -- a 64x64 grid
     // re-reads the 411-MB bf16x2 weight through L2 eight times over (M = 512: 0.80 ms at 130 TFLOP/s algorithmic)
@@ -2293,7 +2225,7 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
     // streaming 1 MB of A each behind a two-stage register pipeline (125 us at 32 images = 2.1 TB/s); split-K slices of the
     // 256-wide tile stream the same rows by DMA (the B rows past N are range-checked away: their MFMAs run on zeros)
     if (!d->tile_hint && !d->conv && d->N <= 64 && d->M >= 256 && d->K >= 2048 && ceil_div(d->M, 256) <= 128 &&
-        !(getenv("WSOVOD_X2_SKINNY") && getenv("WSOVOD_X2_SKINNY")[0] == '0'))
+        !wsovod::env_off("WSOVOD_X2_SKINNY"))
       tile = 2256256;
     // few rows, shorter K (fc2, the stacked heads, the convs of res4 / res5 at 1 - 4 images): re-measured in round 5 on bf16x2
     // operands (tools/small_batch_tiles.py, profiles/r05_small_batch_tiles.md).  T = number of 256x256 tiles:
@@ -2304,23 +2236,23 @@ static int gemm_nt_impl(const wsovod_gemm_desc* d, const wsovod_conv_branches* b
     //   else, K >= 2048    split-K of the 256x256 tile (the stacked heads, N = 1088: 48 vs 70 us)
     if (!d->tile_hint && d->M >= 256 && d->N >= 256 && tile != 2256256 && tile != 256256) {
       auto tiles = [&](int bm, int bn) { return (long long)ceil_div(d->M, bm) * ceil_div(d->N, bn); };
-      const char* cs = getenv("WSOVOD_CONV_SPLITK");  // "1": also convs may take the split form (experiments, tests)
+      const bool cs = wsovod::env_on("WSOVOD_CONV_SPLITK");  // "1": also convs may take the split form (experiments, tests)
       if (tiles(256, 256) >= 150) tile = 2256256;
       else if (tiles(256, 128) >= 200) tile = 256128;
       else if (tiles(128, 64) >= 200) tile = 1128064;
-      else if (d->K >= 2048 && (!d->conv || (cs && cs[0] == '1'))) tile = 2256256;
+      else if (d->K >= 2048 && (!d->conv || cs)) tile = 2256256;
     }
     // the 128-channel convs of res3 at >= 14 images: 512x128 tiles (tools/res3_ab.py, 32 images: 1029 -> 1220, 779 -> 908,
     // 666 -> 828 TFLOP/s executed against 256x128 on the plain / residual / stride-2 layer; bit-identical results)
     if (!d->tile_hint && d->conv && d->N > 64 && d->N <= 128 && (long long)ceil_div(d->M, 512) >= 200 &&
-        !(getenv("WSOVOD_CONV_512") && getenv("WSOVOD_CONV_512")[0] == '0'))
+        !wsovod::env_off("WSOVOD_CONV_512"))
       tile = 512128;
-    if (!d->tile_hint && d->conv && getenv("WSOVOD_CONV_SPLITK") && getenv("WSOVOD_CONV_SPLITK")[0] == '1' && d->M >= 256 &&
+    if (!d->tile_hint && d->conv && wsovod::env_on("WSOVOD_CONV_SPLITK") && d->M >= 256 &&
         d->N >= 256 && d->K >= 2048 && (long long)ceil_div(d->M, 256) * ceil_div(d->N, 256) <= 128)
       tile = 2256256;
     // round 6: the small grids of 1 - 2 images per step behind a deep LDS-DMA pipeline (their K-steps were one DMA round
     // trip each); WSOVOD_X2_DEEP=0: the two-stage forms (A/B runs, bit-identical results)
-    static const bool deep = !(getenv("WSOVOD_X2_DEEP") && getenv("WSOVOD_X2_DEEP")[0] == '0');
+    const bool deep = !wsovod::env_off("WSOVOD_X2_DEEP");
     if (!d->tile_hint && deep) {
       if (tile == 1128064) tile = 3128064;
       else if (tile == 64064 && d->conv && d->K >= 1024 && d->M >= 1024) tile = 3064064;

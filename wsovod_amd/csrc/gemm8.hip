@@ -24,7 +24,6 @@
 // grouped tile order and epilogue as gemm.hip.
 #include "gemm_common.h"
 #include <string.h>
-#include <vector>
 
 namespace wsovod_gemm {
 
@@ -98,12 +97,7 @@ static void branch_grid(GemmBrArgs& args, const GemmArgs& a, int n_branch, const
   args.tiles_per_branch = ceil_div(a.M, 256);
   args.tiles_m = args.tiles_per_branch * n_branch;
   args.tiles_n = ceil_div(a.N, 256);
-  {
-    const int run = std::max(1, args.tiles_m * args.tiles_n / 8);
-    int g = 1;
-    while ((g + 1) * (g + 1) <= run) ++g;
-    args.group_m = std::max(1, std::min(std::min(g, 4), args.tiles_m));
-  }
+  args.group_m = tile_group_height(args.tiles_m, args.tiles_n, 4);
   args.ksplit = args.slice_steps = 0;
   args.m_base = 0;
   for (int b = 0; b < 4; ++b) {
@@ -120,8 +114,7 @@ int launch_gemm256_8ph_branches(const GemmArgs& a, int n_branch, const int* dil,
   static bool attr_set = false;
   constexpr int lds_bytes = 2 * (256 + 256) * 128;
   if (!attr_set) {
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_br_kernel<true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                 "wsovod_gemm_conv_branches: LDS opt-in");
+    WS_OPT_IN_LDS((gemm256_8ph_br_kernel<true, true, 2, true>), lds_bytes, "wsovod_gemm_conv_branches: LDS opt-in");
     attr_set = true;
   }
   GemmBrArgs args;
@@ -141,8 +134,7 @@ int launch_gemm256_8ph_branches_ex(const GemmArgs& a, int n_branch, const int* d
   static bool attr_set = false;
   constexpr int lds_bytes = 2 * (256 + 256) * 128;
   if (!attr_set) {
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_brx_kernel<true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                 "wsovod_gemm_conv_branches_ex: LDS opt-in");
+    WS_OPT_IN_LDS((gemm256_8ph_brx_kernel<true, true, 2, true>), lds_bytes, "wsovod_gemm_conv_branches_ex: LDS opt-in");
     attr_set = true;
   }
   GemmBrExArgs args;
@@ -165,18 +157,11 @@ int launch_gemm256_8ph(const GemmArgs& a, bool conv, hipStream_t s, double flops
   static bool attr_set = false;
   constexpr int lds_bytes = 2 * (256 + 256) * 128;
   if (!attr_set) {
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<true, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<false, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<true, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<false, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_8ph_kernel<true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_nt (8-phase tile): LDS opt-in");
+#define G8_OPT_IN(...) WS_OPT_IN_LDS((gemm256_8ph_kernel<__VA_ARGS__>), lds_bytes, "wsovod_gemm_nt (8-phase tile): LDS opt-in")
+    G8_OPT_IN(false); G8_OPT_IN(true); G8_OPT_IN(false, true); G8_OPT_IN(true, true);
+    G8_OPT_IN(false, false, 2); G8_OPT_IN(true, false, 2); G8_OPT_IN(false, true, 2); G8_OPT_IN(true, true, 2);
+    G8_OPT_IN(false, false, 2, true); G8_OPT_IN(true, false, 2, true); G8_OPT_IN(false, true, 2, true); G8_OPT_IN(true, true, 2, true);
+#undef G8_OPT_IN
     attr_set = true;
   }
   GemmArgs args = a;
@@ -185,15 +170,7 @@ int launch_gemm256_8ph(const GemmArgs& a, bool conv, hipStream_t s, double flops
 #endif
   args.tiles_m = ceil_div(a.M - a.m_base, 256);
   args.tiles_n = ceil_div(a.N, 256);
-  {
-    // Tile-order group height.  What has to share L2 is the set of workgroups an XCD runs AT THE SAME TIME (32 CUs x 1
-    // workgroup), not its whole run of tiles: group_m x (32 / group_m) of them should be near-square.  Measured on the fc1
-    // forward shape (16384 x 4096 x 25088): group 2/4/8/11/16/32 -> 1345/1350/1322/1298/1292/1260 TFLOP/s.
-    const int run = std::max(1, args.tiles_m * args.tiles_n / 8);
-    int g = 1;
-    while ((g + 1) * (g + 1) <= run) ++g;
-    args.group_m = std::max(1, std::min(std::min(g, 4), args.tiles_m));
-  }
+  args.group_m = tile_group_height(args.tiles_m, args.tiles_n, 4);
   // Split-K for contractions with few output tiles and a long K (the FC layers at 1-4 images per step: fc1 forward is
   // 2 x 16 tiles of K = 25088): `ksplit` copies of the grid fill the chip, each reducing a slice of K into a workspace,
   // and a finalize kernel adds the slices and applies the epilogue.  The 256x256 tile keeps the operand traffic through
@@ -205,38 +182,28 @@ int launch_gemm256_8ph(const GemmArgs& a, bool conv, hipStream_t s, double flops
   // where the alternative was a 128x128 / 64x64 grid at 0.12 - 0.25 of peak)
   if (allow_split && ntiles <= 128 && nk >= 32) {
     int S = std::min(std::min(8, 256 / ntiles), nk / 16);
-    if (const char* fs = getenv("WSOVOD_SPLITK_S")) S = std::max(1, std::min(atoi(fs), nk / 4));  // (experiments)
+    const int forced = wsovod::env_int("WSOVOD_SPLITK_S", INT_MIN);  // (experiments)
+    if (forced != INT_MIN) S = std::max(1, std::min(forced, nk / 4));
     if (S >= 2) {
-      // Workspace of this process (single-stream use, as the rest of the library).  A captured HIP graph keeps the
-      // pointer it was captured with, so a block is NEVER freed once handed out: when a larger one is needed the old
-      // block is retired (kept allocated; sizes double, so all retired blocks together are smaller than the live one,
-      // and the largest possible request is 8 slices x 128 tiles = 268 MB), and growing under stream capture is refused
-      // instead of calling hipMalloc inside the capture (the conv forms make `need` shape-dependent).
-      static float* ws = nullptr;
-      static size_t ws_bytes = 0;
-      static std::vector<float*> retired;
+      // Doubling workspace (wsovod::Scratch): the largest possible request is 8 slices x 128 tiles = 268 MB.  Growing under
+      // stream capture is refused (the conv forms make `need` shape-dependent).
+      static wsovod::Scratch ws(wsovod::ScratchGrowth::doubling());
       const long long ldp = ((long long)a.N + 3) / 4 * 4;
       const size_t need = (size_t)S * (a.M - a.m_base) * ldp * sizeof(float);
-      if (need > ws_bytes) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-          wsovod::set_error("wsovod_gemm_nt: the split-K workspace would have to grow under stream capture; run the "
-                            "shape once outside the capture first");
-          return WSOVOD_ERR_UNSUPPORTED;
-        }
-        const size_t want = std::max(need, 2 * ws_bytes);
-        float* fresh = nullptr;
-        if (hipMalloc((void**)&fresh, want) != hipSuccess) {
-          wsovod::set_error("wsovod_gemm_nt: cannot allocate the split-K workspace");
-          return WSOVOD_ERR_HIP;
-        }
-        if (ws) retired.push_back(ws);
-        ws = fresh;
-        ws_bytes = want;
+      wsovod::ScratchStatus st;
+      float* block = (float*)ws.reserve(need, s, &st);
+      if (st == wsovod::ScratchStatus::would_grow_under_capture) {
+        wsovod::set_error("wsovod_gemm_nt: the split-K workspace would have to grow under stream capture; run the "
+                          "shape once outside the capture first");
+        return WSOVOD_ERR_UNSUPPORTED;
+      }
+      if (!block) {
+        wsovod::set_error("wsovod_gemm_nt: cannot allocate the split-K workspace");
+        return WSOVOD_ERR_HIP;
       }
       args.ksplit = S;
       args.slice_steps = ceil_div(nk, S);
-      args.partial = ws;
+      args.partial = block;
       args.partial_ld = ldp;
       grid = ntiles * S;
     }
@@ -247,8 +214,7 @@ int launch_gemm256_8ph(const GemmArgs& a, bool conv, hipStream_t s, double flops
 #define WS_L8(C, X, P) hipLaunchKernelGGL((gemm256_8ph_kernel<C, X, P>), dim3(grid), dim3(512), lds_bytes, s, args)
 #define WS_L8L(C, X) hipLaunchKernelGGL((gemm256_8ph_kernel<C, X, 2, true>), dim3(grid), dim3(512), lds_bytes, s, args)
   // the lean two-phase form: whole K-steps only (no K tail select in front of its DMA instructions)
-  const char* le = getenv("WSOVOD_G8_LEAN");
-  const bool lean = merged && a.K % 64 == 0 && !(le && le[0] == '0') &&
+  const bool lean = merged && a.K % 64 == 0 && !wsovod::env_off("WSOVOD_G8_LEAN") &&
                     (!conv || (a.Cin % 64 == 0 && (!a.A2 || a.Cin2 % 64 == 0) &&
                                a.a_bytes + (long long)(a.pad * a.W + a.pad) * a.Cin * 2 < (1ll << 31)));
   if (a.a_plane && !(lean && x3 && !conv)) {

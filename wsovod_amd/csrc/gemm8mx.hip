@@ -37,7 +37,6 @@
 
 #include <algorithm>
 #include <type_traits>
-#include <vector>
 
 namespace wsovod_gemm {
 namespace {
@@ -322,54 +321,15 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
   MxArgs q;
   memset(&q, 0, sizeof(q));
   GemmArgs& a = q.g;
-  a.A = (const char*)d->A;
-  a.B = (const char*)d->B;
-  a.lda = d->lda * 2;  // counted in 2-byte slots, as the bf16x2 form
-  a.ldb = d->ldb * 2;
-  a.M = d->M;
-  a.N = d->N;
-  a.K = d->K * 2;
-  a.C = d->C;
-  a.ldc = d->ldc;
-  a.dtype_c = d->dtype_c;
-  a.alpha = d->alpha;
-  a.bias = d->bias;
-  a.residual = d->residual;
-  a.ldr = d->ldr;
-  a.dtype_r = d->dtype_r;
-  a.relu = d->relu;
-  a.dropout_p = d->dropout_p;
-  a.seed = d->dropout_seed;
-  a.seed_add = d->dropout_seed_add;
+  fill_gemm_args(a, *d, 2);  // counted in 2-byte slots, as the bf16x2 form
   double bytes;
   if (d->conv) {
     const wsovod_conv_geom& g = d->geom;
     WS_CHECK_ARG(!a_scale, "wsovod_gemm_f16mx(conv): the input map is a unit-scale f16mx tensor (a_scale = NULL)");
     WS_CHECK_ARG(g.Cin > 0 && g.Cin % 32 == 0 && !g.pool, "wsovod_gemm_f16mx(conv): Cin=%d must be a multiple of 32 (no fused pool)", g.Cin);
-    WS_CHECK_ARG(!d->A2 || (d->Cin2 > 0 && d->Cin2 % 32 == 0 && ((uintptr_t)d->A2 & 15) == 0),
-                 "wsovod_gemm_f16mx(conv): the fused shortcut input needs Cin2 (%d) a multiple of 32 and 16-byte alignment", d->Cin2);
-    WS_CHECK_ARG(d->K == g.KH * g.KW * g.Cin + (d->A2 ? d->Cin2 : 0), "wsovod_gemm_f16mx(conv): K=%d != KH*KW*Cin (+ Cin2)", d->K);
-    WS_CHECK_ARG(g.KH * g.KW <= 32, "wsovod_gemm_f16mx(conv): filters of more than 32 taps are not supported (per-tap validity mask)");
-    WS_CHECK_ARG((long long)d->M == (long long)g.n_img * g.Ho * g.Wo, "wsovod_gemm_f16mx(conv): M=%d != n_img*Ho*Wo", d->M);
-    WS_CHECK_ARG(g.stride >= 1 && g.dil >= 1 && g.pad >= 0, "wsovod_gemm_f16mx(conv): bad stride/dil/pad");
-    a.H = g.H; a.W = g.W; a.Cin = g.Cin * 2; a.Ho = g.Ho; a.Wo = g.Wo;
-    a.KH = g.KH; a.KW = g.KW; a.stride = g.stride; a.pad = g.pad; a.dil = g.dil;
-    a.a_bytes = (long long)g.n_img * g.H * g.W * g.Cin * 4;
-    if (br) {  // the 2 GiB limit is kept for the WHOLE n_branch * N operand, with the largest branch's border in front
-      int pmax = 0;
-      for (int b = 0; b < br->n_branch; ++b) pmax = std::max(pmax, br->pad[b]);
-      WS_CHECK_ARG(a.a_bytes * (br->shared_input ? 1 : br->n_branch) + (long long)(pmax * g.W + pmax) * g.Cin * 4 < (1ll << 31) &&
-                       (long long)d->M * br->n_branch < (1ll << 31),
-                   "wsovod_gemm_f16mx_conv_branches: the n_branch * N input exceeds the 2 GiB buffer-addressing limit");
-    }
-    if (d->A2) {
-      a.A2 = (const char*)d->A2;
-      a.Cin2 = d->Cin2 * 2;
-      a.a2_bytes = (long long)g.n_img * g.Ho * g.Wo * d->Cin2 * 4;
-      WS_CHECK_ARG(a.a2_bytes < (1ll << 31), "wsovod_gemm_f16mx(conv): fused shortcut input exceeds the 2 GiB buffer-addressing limit");
-    }
-    WS_CHECK_ARG(a.a_bytes + (long long)(g.pad * g.W + g.pad) * g.Cin * 4 < (1ll << 31),
-                 "wsovod_gemm_f16mx(conv): input of %lld bytes exceeds the 2 GiB buffer-addressing limit", a.a_bytes);
+    if (int rc = check_and_fill_conv(a, *d, 2, 2, 32, /*border_in_limit=*/true, "wsovod_gemm_f16mx")) return rc;
+    if (br)
+      if (int rc = check_branch_limit(a, *br, "wsovod_gemm_f16mx_conv_branches")) return rc;
     bytes = ((double)g.n_img * g.H * g.W * g.Cin + (double)d->N * d->K + (d->A2 ? (double)d->M * d->Cin2 : 0.0)) * 4.0;
   } else {
     WS_CHECK_ARG(a_segments == 1 || a_scale, "wsovod_gemm_f16mx: scale segments without a scale array");
@@ -382,12 +342,7 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
   if (br) bytes = bytes * nbr - (double)(nbr - 1) * d->N * d->K * 4.0;  // (the weight is read once)
   a.tiles_m = (d->M + 255) / 256 * nbr;
   a.tiles_n = (d->N + 255) / 256;
-  {
-    const int run = std::max(1, a.tiles_m * a.tiles_n / 8);
-    int g = 1;
-    while ((g + 1) * (g + 1) <= run) ++g;
-    a.group_m = std::max(1, std::min(std::min(g, 4), a.tiles_m));
-  }
+  a.group_m = tile_group_height(a.tiles_m, a.tiles_n, 4);
   q.sa = d->conv ? nullptr : a_scale;
   q.sb = b_scale;
   q.nseg_a = a_scale ? a_segments : 1;
@@ -401,19 +356,13 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
   static bool attr_set = false;
   constexpr int lds_bytes = (3 * 256 + 2 * 256) * 128;  // 160 KiB: the whole CU
   if (!attr_set) {
-#define MX_OPT_IN(C, E)                                                                                                  \
-  WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_mx_kernel<C, E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), \
-               "wsovod_gemm_f16mx: LDS opt-in")
+#define MX_OPT_IN(C, E) WS_OPT_IN_LDS((gemm256_mx_kernel<C, E>), lds_bytes, "wsovod_gemm_f16mx: LDS opt-in")
     MX_OPT_IN(false, 0); MX_OPT_IN(false, 1); MX_OPT_IN(false, 4);
     MX_OPT_IN(true, 0); MX_OPT_IN(true, 1); MX_OPT_IN(true, 2); MX_OPT_IN(true, 3);
 #undef MX_OPT_IN
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_mx_br_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                 "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_mx_br_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                 "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
-#define MX_OPT_IN_X(E)                                                                                                       \
-  WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm256_mx_brx_kernel<true, E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), \
-               "wsovod_gemm_f16mx_conv_branches_ex: LDS opt-in")
+    WS_OPT_IN_LDS((gemm256_mx_br_kernel<true, 0>), lds_bytes, "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
+    WS_OPT_IN_LDS((gemm256_mx_br_kernel<true, 1>), lds_bytes, "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
+#define MX_OPT_IN_X(E) WS_OPT_IN_LDS((gemm256_mx_brx_kernel<true, E>), lds_bytes, "wsovod_gemm_f16mx_conv_branches_ex: LDS opt-in")
     MX_OPT_IN_X(0); MX_OPT_IN_X(1); MX_OPT_IN_X(2); MX_OPT_IN_X(3);
 #undef MX_OPT_IN_X
     attr_set = true;
@@ -426,20 +375,13 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
   // again (res5: 84 tiles x 3 = 252).  Measured (tools/mx_conv_ab.py, 32 images): res5 1.833 -> 1.780 ms per conv; a last
   // round that is more than half full (res4: 170 tiles) is left alone -- its slices' workspace traffic and shorter K loops cost
   // more than the idle CUs, which the chip gives back as clock under its power limit (0.509 -> 0.560 ms with 170 x 3).
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) n_cu = 256;
-    else n_cu = std::max(1, prop.multiProcessorCount);
-    (void)hipGetLastError();
-  }
+  const int n_cu = wsovod::cu_count();
   const int ntiles = a.tiles_m * a.tiles_n, nk_all = a.K / 64;
   int tail_mt = 0, S = 1;
   {
-    const char* ts = getenv("WSOVOD_MX_TAIL");  // (A/B runs: 0 = one launch)
     // (the branch-batched form keeps ONE launch: its last round is the branches' last tiles, whose rows are not contiguous)
-    const bool on = !br && !(ts && ts[0] == '0') && q.nseg_a == 1 && q.nseg_b == 1 && n_cu % a.tiles_n == 0 && nk_all >= 24;
+    // (WSOVOD_MX_TAIL=0: one launch; A/B runs)
+    const bool on = !br && !wsovod::env_off("WSOVOD_MX_TAIL") && q.nseg_a == 1 && q.nseg_b == 1 && n_cu % a.tiles_n == 0 && nk_all >= 24;
     const int rem = ntiles % n_cu;
     if (on && ntiles > n_cu && rem != 0 && rem % a.tiles_n == 0 && 2 * rem <= n_cu) {
       double best = 1.0 + 0.02;
@@ -451,32 +393,15 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
     }
   }
   if (tail_mt > 0) {
-    // workspace of this process (single-stream use, as the rest of the library): never freed once handed out -- a captured
-    // HIP graph keeps the pointer --, growing under stream capture is refused (the policy of gemm8.hip's split-K workspace)
-    static float* ws = nullptr;
-    static size_t ws_bytes = 0;
-    static std::vector<float*> retired;
+    // doubling workspace (wsovod::Scratch); where it would have to grow under stream capture, or cannot be allocated, the
+    // conv silently runs as the single launch -- another summation order for the last round's rows than outside the capture
+    static wsovod::Scratch ws(wsovod::ScratchGrowth::doubling());
     const int m_base = (a.tiles_m - tail_mt) * 256;
     const long long ldp = ((long long)d->N + 3) / 4 * 4;
-    const size_t need = (size_t)S * (d->M - m_base) * ldp * sizeof(float);
-    if (need > ws_bytes) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-      float* fresh = nullptr;
-      const size_t want = std::max(need, 2 * ws_bytes);
-      if (capturing || hipMalloc((void**)&fresh, want) != hipSuccess) {
-        (void)hipGetLastError();
-        tail_mt = 0;  // (no workspace: the single launch)
-      } else {
-        if (ws) retired.push_back(ws);
-        ws = fresh;
-        ws_bytes = want;
-      }
-    }
-    if (tail_mt > 0) {
-      a.partial = ws;
-      a.partial_ld = ldp;
-    }
+    wsovod::ScratchStatus st;
+    a.partial = (float*)ws.reserve((size_t)S * (d->M - m_base) * ldp * sizeof(float), s, &st);
+    if (a.partial) a.partial_ld = ldp;
+    else tail_mt = 0;
   }
   static int slot_b = wsovod::prof_slot("conv_igemm_f16mx_256x256_8ph_branches");
   static int slot_bx = wsovod::prof_slot("conv_igemm_f16mx_256x256_8ph_branches_ex");
@@ -560,12 +485,7 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
     qt.g.tiles_m = tail_mt;
     qt.g.ksplit = S;
     qt.g.slice_steps = (nk_all + S - 1) / S;
-    {
-      const int run = std::max(1, tail_mt * a.tiles_n / 8);
-      int g = 1;
-      while ((g + 1) * (g + 1) <= run) ++g;
-      qt.g.group_m = std::max(1, std::min(std::min(g, 4), tail_mt));
-    }
+    qt.g.group_m = tile_group_height(tail_mt, a.tiles_n, 4);
     launch(qt, tail_mt * a.tiles_n * S);
     const long long quads = (long long)(d->M - m_base) * (d->N / 4);
     hipLaunchKernelGGL(mx_splitk_finalize_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, qt);

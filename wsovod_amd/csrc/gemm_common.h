@@ -1,5 +1,7 @@
 // Pieces shared by the GEMM / implicit-GEMM kernels (gemm.hip: generic tiles; gemm8.hip: the 8-phase 256x256 tile).
 #pragma once
+#include <limits.h>
+
 #include "common.h"
 
 namespace wsovod_gemm {
@@ -66,6 +68,78 @@ struct GemmBrArgs : GemmArgs {
 struct GemmBrExArgs : GemmBrArgs {
   long long r_branch_bytes;
 };
+
+// ---- host side: what every front does before it picks a kernel
+
+// Tile-order group height (the XCD remap of the kernels walks groups of group_m row tiles).  What has to share L2 is the set
+// of workgroups an XCD runs AT THE SAME TIME (32 CUs x 1 workgroup), not its whole run of tiles: group_m x (32 / group_m) of
+// them should be near-square, hence the cap of the one-workgroup-per-CU 256x256 tiles (INT_MAX: the square root of the run).
+// Measured on the fc1 forward shape (16384 x 4096 x 25088): group 2/4/8/11/16/32 -> 1345/1350/1322/1298/1292/1260 TFLOP/s.
+inline int tile_group_height(int tiles_m, int tiles_n, int cap) {
+  const int run = std::max(1, tiles_m * tiles_n / 8);  // tiles per XCD
+  int g = 1;
+  while ((g + 1) * (g + 1) <= run) ++g;
+  return std::max(1, std::min(std::min(g, cap), tiles_m));
+}
+
+// The descriptor's fields as the kernels take them.  A value is `slots` operand elements wide (bf16x2, f16mx: 2), so the
+// leading dimensions and K are counted in slots; a planar A row holds lda bf16 values, the interleaved row slots * lda
+inline void fill_gemm_args(GemmArgs& a, const wsovod_gemm_desc& d, int slots) {
+  memset(&a, 0, sizeof(a));
+  a.A = (const char*)d.A, a.B = (const char*)d.B;
+  a.a_plane = d.a_plane_bytes, a.lda = d.a_plane_bytes ? d.lda : d.lda * slots, a.ldb = d.ldb * slots;
+  a.M = d.M, a.N = d.N, a.K = d.K * slots;
+  a.C = d.C, a.ldc = d.ldc, a.dtype_c = d.dtype_c;
+  a.Ct = d.Ct, a.ldct = d.ldct, a.dtype_ct = d.dtype_ct;
+  a.alpha = d.alpha, a.row_scale = d.row_scale, a.bias = d.bias;
+  a.residual = d.residual, a.ldr = d.ldr, a.dtype_r = d.dtype_r;
+  a.relu = d.relu, a.dropout_p = d.dropout_p, a.seed = d.dropout_seed, a.seed_add = d.dropout_seed_add;
+  a.row_group = d.row_group, a.group_add = d.group_add, a.ld_ga = d.ld_ga;
+  a.mask_src = d.mask_src, a.ldm = d.ldm, a.dtype_m = d.dtype_m, a.mask_scale = d.mask_scale;
+  a.accumulate = d.accumulate;
+}
+
+// The implicit-GEMM conv form: the checks every conv kernel relies on, then the geometry and the operands' byte sizes
+// (slots of slot_bytes each per value; Cin, Cin2 multiples of cin_multiple values).  border_in_limit: the 2 GiB limit of the
+// input counts the pad border in front of it.  The f16mx front asks for that; the bf16 / bf16x2 / fp32 front does not (its lean
+// 8-wavefront tile tests the border itself and leaves such an input to the general form).  The two fronts were found to
+// differ in this and still do: the flag keeps the difference at the call sites.  `who`: the entry's name in the messages.
+inline int check_and_fill_conv(GemmArgs& a, const wsovod_gemm_desc& d, int slots, int slot_bytes, int cin_multiple,
+                               bool border_in_limit, const char* who) {
+  const wsovod_conv_geom& g = d.geom;
+  WS_CHECK_ARG(g.Cin > 0 && g.Cin % cin_multiple == 0, "%s(conv): Cin=%d must be a multiple of %d", who, g.Cin, cin_multiple);
+  WS_CHECK_ARG(!d.A2 || (d.Cin2 > 0 && d.Cin2 % cin_multiple == 0 && ((uintptr_t)d.A2 & 15) == 0),
+               "%s(conv): the fused shortcut input needs Cin2 (%d) a multiple of %d and 16-byte alignment", who, d.Cin2, cin_multiple);
+  WS_CHECK_ARG(d.K == g.KH * g.KW * g.Cin + (d.A2 ? d.Cin2 : 0), "%s(conv): K=%d != KH*KW*Cin (+ Cin2)", who, d.K);
+  WS_CHECK_ARG(g.KH * g.KW <= 32, "%s(conv): filters of more than 32 taps are not supported (per-tap validity mask)", who);
+  WS_CHECK_ARG((long long)d.M == (long long)g.n_img * g.Ho * g.Wo, "%s(conv): M=%d != n_img*Ho*Wo", who, d.M);
+  WS_CHECK_ARG(g.stride >= 1 && g.dil >= 1 && g.pad >= 0, "%s(conv): bad stride/dil/pad", who);
+  const int vbytes = slots * slot_bytes;
+  a.H = g.H, a.W = g.W, a.Cin = g.Cin * slots, a.Ho = g.Ho, a.Wo = g.Wo;
+  a.KH = g.KH, a.KW = g.KW, a.stride = g.stride, a.pad = g.pad, a.dil = g.dil, a.pool = g.pool;
+  a.a_bytes = (long long)g.n_img * g.H * g.W * g.Cin * vbytes;
+  if (d.A2) {
+    a.A2 = (const char*)d.A2;
+    a.Cin2 = d.Cin2 * slots;
+    a.a2_bytes = (long long)g.n_img * g.Ho * g.Wo * d.Cin2 * vbytes;
+    WS_CHECK_ARG(a.a2_bytes < (1ll << 31), "%s(conv): fused shortcut input exceeds the 2 GiB buffer-addressing limit", who);
+  }
+  const long long border = border_in_limit ? (long long)(g.pad * g.W + g.pad) * g.Cin * vbytes : 0;
+  WS_CHECK_ARG(a.a_bytes + border < (1ll << 31), "%s(conv): input of %lld bytes exceeds the 2 GiB buffer-addressing limit", who,
+               a.a_bytes);
+  return WSOVOD_OK;
+}
+
+// The branch-batched conv (2-byte slots): the 2 GiB limit is kept for the WHOLE n_branch * N operand, with the largest
+// branch's border in front.  `who`: wsovod_gemm_conv_branches / wsovod_gemm_f16mx_conv_branches
+inline int check_branch_limit(const GemmArgs& a, const wsovod_conv_branches& br, const char* who) {
+  int pmax = 0;
+  for (int b = 0; b < br.n_branch; ++b) pmax = std::max(pmax, br.pad[b]);
+  WS_CHECK_ARG(a.a_bytes * (br.shared_input ? 1 : br.n_branch) + (long long)(pmax * a.W + pmax) * a.Cin * 2 < (1ll << 31) &&
+                   (long long)a.M * br.n_branch < (1ll << 31),
+               "%s: the n_branch * N input exceeds the 2 GiB buffer-addressing limit", who);
+  return WSOVOD_OK;
+}
 
 template <typename T>
 struct Traits;

@@ -18,7 +18,6 @@
 // earlier, which is read one phase later.  A row half is overwritten two phases after its last read.
 #include "gemm_common.h"
 #include "f16mx.h"
-#include <vector>
 
 namespace wsovod_gemm {
 
@@ -698,28 +697,24 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
     a.lr_dev = upd->lr_dev;
   }
 #if defined(TN_STAMPS)
-  a.dbg = getenv("WSOVOD_TN_DEBUG_PTR") ? (float*)strtoull(getenv("WSOVOD_TN_DEBUG_PTR"), nullptr, 16) : nullptr;
+  const char* dp = getenv("WSOVOD_TN_DEBUG_PTR");
+  a.dbg = dp ? (float*)strtoull(dp, nullptr, 16) : nullptr;
 #endif
   a.tiles_i = ceil_div(NI, 256);
   a.tiles_j = ceil_div(NJ, 256);
-  {
-    const int run = std::max(1, a.tiles_i * a.tiles_j / 8);
-    int g = 1;
-    while ((g + 1) * (g + 1) <= run) ++g;
-    // near-square CONCURRENT set per XCD (32 workgroups), see gemm8.hip; fc1 dW shape: group 4/8/14/16 -> 1197/1207/1154/1172
-    a.group_m = std::max(1, std::min(std::min(g, 8), a.tiles_i));
-  }
+  // near-square CONCURRENT set per XCD (32 workgroups), see tile_group_height; fc1 dW shape: group 4/8/14/16 -> 1197/1207/1154/1172
+  a.group_m = wsovod_gemm::tile_group_height(a.tiles_i, a.tiles_j, 8);
   static int slot_plain = wsovod::prof_slot("gemm_tn_bf16_256x256_tr");
   static int slot_sgd = wsovod::prof_slot("gemm_tn_bf16_256x256_tr_sgd");
   const int slot = upd ? slot_sgd : slot_plain;
   static bool attr_set = false;
   constexpr int lds_bytes = 2 * 2 * 2 * 64 * 256;  // 2 K-steps x (P, Q) x 2 sub-images x 64 rows x 256 B = 128 KiB
   if (!attr_set) {
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn8_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_tn: LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn8_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "wsovod_gemm_tn: LDS opt-in");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn8_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "wsovod_gemm_tn: LDS opt-in (160 KiB)");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn8_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "wsovod_gemm_tn_sgd: LDS opt-in (160 KiB)");
-    WS_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn8_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "wsovod_gemm_tn_sgd (tail): LDS opt-in (160 KiB)");
+    WS_OPT_IN_LDS(gemm_tn8_kernel<0>, lds_bytes, "wsovod_gemm_tn: LDS opt-in");
+    WS_OPT_IN_LDS(gemm_tn8_kernel<1>, lds_bytes, "wsovod_gemm_tn: LDS opt-in");
+    WS_OPT_IN_LDS(gemm_tn8_kernel<2>, 160 * 1024, "wsovod_gemm_tn: LDS opt-in (160 KiB)");
+    WS_OPT_IN_LDS((gemm_tn8_kernel<2, true>), 160 * 1024, "wsovod_gemm_tn_sgd: LDS opt-in (160 KiB)");
+    WS_OPT_IN_LDS((gemm_tn8_kernel<2, false, true>), 160 * 1024, "wsovod_gemm_tn_sgd (tail): LDS opt-in (160 KiB)");
     attr_set = true;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -748,7 +743,7 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
       grid = ntiles * S;
     }
   } else if (!(accumulate & 2) && ntiles > cus && tail > 0 && tail <= cus / 2 &&
-             !(getenv("WSOVOD_TN_TAIL") && getenv("WSOVOD_TN_TAIL")[0] == '0')) {
+             !wsovod::env_off("WSOVOD_TN_TAIL")) {
     const int S = std::min(8, cus / tail);
     if (nk >= 8 * S) {
       a.full_tiles = ntiles - tail;
@@ -759,57 +754,46 @@ static int tn_launch(const void* P, long long ldp, const void* Q, long long ldq,
   }
   a.partial = nullptr;
   if (a.ksplit && !upd) {
-    // Workspace of this process (single-stream use, as the rest of the library; the pattern of gemm8.hip's split-K): its
-    // largest possible size (at most 256 slices x 256 KB = 64 MB: split tiles x slices never exceed the 256 CUs) is
-    // allocated at the first split launch and never freed -- a captured HIP graph keeps the pointer it was captured
-    // with -- so it never has to grow.  A first split launch under stream capture is refused, as gemm8's split-K does.
-    static float* ws = nullptr;
-    if (!ws) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-        wsovod::set_error("wsovod_gemm_tn: the split-K workspace is allocated at the first split launch, not under stream "
-                          "capture; run a split shape once outside the capture first");
-        return WSOVOD_ERR_UNSUPPORTED;
-      }
-      if (hipMalloc((void**)&ws, (size_t)cus * 65536 * sizeof(float)) != hipSuccess) {
-        ws = nullptr;
-        wsovod::set_error("wsovod_gemm_tn: cannot allocate the split-K workspace");
-        return WSOVOD_ERR_HIP;
-      }
+    // Workspace (wsovod::Scratch) of the largest possible size (at most 256 slices x 256 KB = 64 MB: split tiles x slices
+    // never exceed the 256 CUs), allocated at the first split launch, so it never has to grow.  A first split launch under
+    // stream capture is refused, as gemm8's split-K does.
+    constexpr size_t ws_bytes = (size_t)cus * 65536 * sizeof(float);
+    static wsovod::Scratch ws(wsovod::ScratchGrowth::fixed_size(ws_bytes));
+    wsovod::ScratchStatus st;
+    a.partial = (float*)ws.reserve(ws_bytes, s, &st);
+    if (st == wsovod::ScratchStatus::would_grow_under_capture) {
+      wsovod::set_error("wsovod_gemm_tn: the split-K workspace is allocated at the first split launch, not under stream "
+                        "capture; run a split shape once outside the capture first");
+      return WSOVOD_ERR_UNSUPPORTED;
     }
-    a.partial = ws;
+    if (!a.partial) {
+      wsovod::set_error("wsovod_gemm_tn: cannot allocate the split-K workspace");
+      return WSOVOD_ERR_HIP;
+    }
   }
-  static const int lean = getenv("WSOVOD_TN_LEAN") ? atoi(getenv("WSOVOD_TN_LEAN")) : 2;
+  static const int lean = wsovod::env_int("WSOVOD_TN_LEAN", 2);
   if (upd) {
     // The update needs the finished sum of a tile in one place: whole tiles, the fused epilogue.  WSOVOD_TN_SGD_TAIL=1
     // (measured and NOT the default): a last round that fills less than half the chip cut along K as the plain form does,
     // its slices meeting by atomics in a compact scratch and a small pass applying the update of those tiles from it --
     // fc1 (1568 tiles = 6 rounds + 32) at 1 image 0.526 against 0.496 ms for fc1 + fc2, at 8 images 0.969 against 0.944: the
     // memset + atomics + extra pass cost more than the partly filled round at these reduction lengths.
-    const bool want_tail = ntiles > cus && tail > 0 && tail <= cus / 2 &&
-                           getenv("WSOVOD_TN_SGD_TAIL") && getenv("WSOVOD_TN_SGD_TAIL")[0] == '1';
+    const bool want_tail = ntiles > cus && tail > 0 && tail <= cus / 2 && wsovod::env_on("WSOVOD_TN_SGD_TAIL");
     const int S = want_tail ? std::min(8, cus / tail) : 0;
     if (want_tail && S >= 2 && nk >= 8 * S) {
-      static float* tb = nullptr;
-      static size_t tb_bytes = 0;
-      static std::vector<float*> retired;  // (never freed: a captured step graph keeps the pointer it was captured with)
+      // (doubling up to the largest tail: half the CUs' tiles)
+      static wsovod::Scratch tail_scratch(wsovod::ScratchGrowth::doubling_capped((size_t)128 * 65536 * sizeof(float)));
       const size_t need = (size_t)tail * 65536 * sizeof(float);
-      if (need > tb_bytes) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-          wsovod::set_error("wsovod_gemm_tn_sgd: the tail scratch would have to grow under stream capture; run the shape once "
-                            "outside the capture first");
-          return WSOVOD_ERR_UNSUPPORTED;
-        }
-        float* fresh = nullptr;
-        const size_t want = std::max(need, std::min<size_t>(2 * tb_bytes, (size_t)128 * 65536 * sizeof(float)));
-        if (hipMalloc((void**)&fresh, want) != hipSuccess) {
-          wsovod::set_error("wsovod_gemm_tn_sgd: cannot allocate the tail scratch");
-          return WSOVOD_ERR_HIP;
-        }
-        if (tb) retired.push_back(tb);
-        tb = fresh;
-        tb_bytes = want;
+      wsovod::ScratchStatus st;
+      float* tb = (float*)tail_scratch.reserve(need, s, &st);
+      if (st == wsovod::ScratchStatus::would_grow_under_capture) {
+        wsovod::set_error("wsovod_gemm_tn_sgd: the tail scratch would have to grow under stream capture; run the shape once "
+                          "outside the capture first");
+        return WSOVOD_ERR_UNSUPPORTED;
+      }
+      if (!tb) {
+        wsovod::set_error("wsovod_gemm_tn_sgd: cannot allocate the tail scratch");
+        return WSOVOD_ERR_HIP;
       }
       a.tail_buf = tb;
       a.full_tiles = ntiles - tail;

@@ -672,20 +672,14 @@ int wsovod_image_bce_backward(const float* dS_img, const int* seg_offsets, int G
 }
 
 // per-block partial sums of the two loss kernels (at most kLossBlocks blocks each, one slot range per kernel): allocated
-// once, never freed (a captured HIP graph keeps the pointer); nullptr when the first call is under stream capture -- the
-// kernels then add their block sums by atomics
+// once (wsovod::Scratch); nullptr when the first call is under stream capture -- the kernels then add their block sums by
+// atomics
 constexpr int kLossBlocks = 256;
 static float* loss_parts(hipStream_t s) {
-  static float* ws = nullptr;
-  if (!ws) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return nullptr;
-    if (hipMalloc((void**)&ws, 2 * kLossBlocks * sizeof(float)) != hipSuccess) {
-      (void)hipGetLastError();
-      ws = nullptr;
-    }
-  }
-  return ws;
+  constexpr size_t bytes = 2 * kLossBlocks * sizeof(float);
+  static wsovod::Scratch ws(wsovod::ScratchGrowth::fixed_size(bytes));
+  wsovod::ScratchStatus st;
+  return (float*)ws.reserve(bytes, s, &st);
 }
 
 int wsovod_weighted_ce_forward(const float* logits, long long ld, int M, int K1, const long long* gt_classes,

@@ -451,7 +451,7 @@ int wsovod_nms_segments(const float* boxes, const int* seg_offsets, const unsign
   {
     static bool attr_set = false;
     if (!attr_set) {
-      WS_CHECK_HIP(hipFuncSetAttribute((const void*)nms_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024), "wsovod_nms_segments: LDS opt-in");
+      WS_OPT_IN_LDS(nms_scan_kernel, 159 * 1024, "wsovod_nms_segments: LDS opt-in");
       attr_set = true;
     }
     wsovod::ProfScope prof(slot_s, s, 0.0, (double)N * W * 8);

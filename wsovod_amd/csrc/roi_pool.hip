@@ -1520,14 +1520,14 @@ static int roi_pool_forward_impl(const void* feat, int dtype, int layout, const 
         const int g2 = (int)std::min<long long>(ceil_div_ll(total_vec, 256), 256 * 64);
         wsovod::ProfScope prof2(slot2, s, 0.0, 2.0 * (double)N * C * H * W * esz);
         // strips of 8 rows per thread (WSOVOD_ROIPOOL_M2_STRIP=0: one output per thread; A/B runs)
-        const char* ms = getenv("WSOVOD_ROIPOOL_M2_STRIP");
+        const bool strip = !wsovod::env_off("WSOVOD_ROIPOOL_M2_STRIP");
         constexpr int RH = 8;
         const long long total_strip = (long long)N * ceil_div(H, RH) * W * (C / v);
         const int g3 = (int)std::min<long long>(ceil_div_ll(total_strip, 256), 256 * 64);
-        if (!(ms && ms[0] == '0') && dtype == WSOVOD_BF16)
+        if (strip && dtype == WSOVOD_BF16)
           hipLaunchKernelGGL((max2x2_s1_strip_nhwc<bf16_t, 8, RH>), dim3(g3), dim3(256), 0, s, (const bf16_t*)feat,
                              (bf16_t*)workspace, H, W, C, total_strip);
-        else if (!(ms && ms[0] == '0'))
+        else if (strip)
           hipLaunchKernelGGL((max2x2_s1_strip_nhwc<float, 4, RH>), dim3(g3), dim3(256), 0, s, (const float*)feat,
                              (float*)workspace, H, W, C, total_strip);
         else if (dtype == WSOVOD_BF16)

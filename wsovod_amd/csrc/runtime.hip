@@ -17,6 +17,33 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+void* HipScratchApi::alloc(size_t bytes) {
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) == hipSuccess) return p;
+  (void)hipGetLastError();
+  return nullptr;
+}
+bool HipScratchApi::capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+int HipScratchApi::device() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess ? dev : 0;
+}
+
+int cu_count() {
+  static std::vector<int> n_cu;
+  const size_t dev = (size_t)std::max(0, HipScratchApi::device());
+  if (dev >= n_cu.size()) n_cu.resize(dev + 1, 0);
+  if (!n_cu[dev]) {
+    hipDeviceProp_t prop;
+    n_cu[dev] = hipGetDeviceProperties(&prop, (int)dev) == hipSuccess ? std::max(1, prop.multiProcessorCount) : 256;
+    (void)hipGetLastError();
+  }
+  return n_cu[dev];
+}
+
 // ---------------------------------------------------------------------------------
 // Profiling table.  Slots are registered lazily by name; ProfScope brackets a launch
 // with two events on the launch stream and parks the pair until collect().

@@ -815,6 +815,67 @@ int wsovod_transform_proposals(const wsovod_proposal_batch* batch, const float* 
                                int topk, void* workspace, long long workspace_bytes, float* out_boxes, float* out_logits,
                                int* out_count, wsovod_stream_t stream);
 
+/* Random crop in the training input stage (MODEL.HIP.INPUT_CROP; data/dataset_mapper.py:88-89 puts detectron2's
+ * T.RandomCrop(INPUT.CROP.TYPE, INPUT.CROP.SIZE) in front of ResizeShortestEdge and RandomFlip of :144-191; its CropTransform
+ * is img[y0:y0+ch, x0:x0+cw] on the image and x -= x0, y -= y0 on coordinates).  The two entries below are the two entries
+ * above with the crop: the same kernels, which the entries above drive with a whole-image window / no crop.
+ *
+ * wsovod_resample_u8_batch_win.  wsovod_resample_u8_batch with each image read through a window of its source, so that
+ * CropTransform.apply_image, ResizeTransform.apply_image, HFlipTransform.apply_image and the padding are the same two
+ * launches.  Per image:
+ *   src        device pointer to the window's first sample of channel 0;
+ *   src_bytes  bytes readable from src;
+ *   H, W       the window's size = the resize input (a crop: ch, cw);
+ *   stride_c / stride_y / stride_x  byte strides from a sample to the same sample of the next channel / row / pixel, all
+ *              positive and below 2^31, stride_x 1 or 3 (plane-major: H_src * W_src, W_src, 1; interleaved: 1, 3 * W_src, 3);
+ *   flip       mirror the output;
+ *   kk_* / bounds_* / ksize_* / tmp  as for wsovod_resample_u8_batch, for the window's sizes.
+ * Everything wsovod_resample_u8_batch validates is validated, and 2 * stride_c + (H - 1) * stride_y + (W - 1) * stride_x <
+ * src_bytes (the window's last sample is readable) before anything is launched.  The kernels read the source byte by byte
+ * -- a window's start and pitch are not 4-byte aligned in general -- and never a byte outside the window's own rows and
+ * columns. */
+typedef struct {
+  const unsigned char* src;
+  long long src_bytes;
+  long long stride_c, stride_y;
+  int stride_x;
+  int H, W, nh, nw;
+  int flip;
+  int kk_h, bounds_h, ksize_h;
+  int kk_v, bounds_v, ksize_v;
+  long long tmp;
+} wsovod_resample_window;
+typedef struct {
+  int n;
+  wsovod_resample_window img[WSOVOD_INPUT_MAX_IMAGES];
+} wsovod_resample_window_batch;
+int wsovod_resample_u8_batch_win(const wsovod_resample_window_batch* batch, const int* tables, long long table_ints,
+                                 unsigned char* scratch, long long scratch_bytes, unsigned char* canvas, int Hp, int Wp,
+                                 wsovod_stream_t stream);
+
+/* wsovod_transform_proposals_win.  wsovod_transform_proposals (detection_utils.py:206-265, transform_proposals and
+ * unique_boxes) under TransformList([CropTransform, ResizeTransform, HFlipTransform?]): with has_crop != 0 step 1 begins,
+ * per corner, with x = x - crop_x and y = y - crop_y (float32 differences of their own, nothing contracted), then the scale
+ * and the flip as above with sx = float32(new_w / cw), sy = float32(new_h / ch).  Steps 2 - 5, the workspace query, the
+ * table and the launches are wsovod_transform_proposals'.  Refused with WSOVOD_ERR_UNSUPPORTED in addition: crop offsets
+ * that are not whole numbers in [0, 4e6] (exact in float32, as the host subtracts an int). */
+typedef struct {
+  int start, count;
+  float sx, sy;
+  int flip;
+  float flip_w, clip_w, clip_h;
+  int has_crop;
+  float crop_x, crop_y;
+  int reserved;
+} wsovod_proposal_window;
+typedef struct {
+  int n;
+  wsovod_proposal_window img[WSOVOD_INPUT_MAX_IMAGES];
+} wsovod_proposal_window_batch;
+int wsovod_transform_proposals_win(const wsovod_proposal_window_batch* batch, const float* boxes, const float* logits,
+                                   int total_rows, int topk, void* workspace, long long workspace_bytes, float* out_boxes,
+                                   float* out_logits, int* out_count, wsovod_stream_t stream);
+
 /* Proposal sub-sampling for the refinement losses, no grad.  Replaces detectron2 `subsample_labels` as called by
  * WSOVODROIHeads._sample_proposals_wsl (roi_heads.py:1566-1603) when an image has more proposals than
  * WSOVOD.SAMPLING.BATCH_SIZE_PER_IMAGE or POSITIVE_FRACTION < 1 (the shipped RPN configs: up to 4000 loaded + 1024

@@ -97,6 +97,29 @@ class ProposalBatch(C.Structure):
     _fields_ = [("n", C.c_int), ("img", ProposalImage * INPUT_MAX_IMAGES)]
 
 
+class ResampleWindow(C.Structure):
+    """wsovod_resample_window (include/wsovod_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_longlong), ("stride_c", C.c_longlong), ("stride_y", C.c_longlong)] + [
+        (n, C.c_int) for n in ("stride_x", "H", "W", "nh", "nw", "flip", "kk_h", "bounds_h", "ksize_h", "kk_v", "bounds_v",
+                               "ksize_v")] + [("tmp", C.c_longlong)]
+
+
+class ResampleWindowBatch(C.Structure):
+    """wsovod_resample_window_batch (include/wsovod_hip.h)."""
+    _fields_ = [("n", C.c_int), ("img", ResampleWindow * INPUT_MAX_IMAGES)]
+
+
+class ProposalWindow(C.Structure):
+    """wsovod_proposal_window (include/wsovod_hip.h)."""
+    _fields_ = ProposalImage._fields_ + [("has_crop", C.c_int), ("crop_x", C.c_float), ("crop_y", C.c_float),
+                                         ("reserved", C.c_int)]
+
+
+class ProposalWindowBatch(C.Structure):
+    """wsovod_proposal_window_batch (include/wsovod_hip.h)."""
+    _fields_ = [("n", C.c_int), ("img", ProposalWindow * INPUT_MAX_IMAGES)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_longlong), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -198,6 +221,8 @@ SIGNATURES = {
     "wsovod_resample_u8_batch": [C.POINTER(ResampleBatch), _P, _L, _P, _L, _P, _I, _I, _P],
     "wsovod_transform_proposals_workspace_bytes": [_I],
     "wsovod_transform_proposals": [C.POINTER(ProposalBatch), _P, _P, _I, _I, _P, _L, _P, _P, _P, _P],
+    "wsovod_resample_u8_batch_win": [C.POINTER(ResampleWindowBatch), _P, _L, _P, _L, _P, _I, _I, _P],
+    "wsovod_transform_proposals_win": [C.POINTER(ProposalWindowBatch), _P, _P, _I, _I, _P, _L, _P, _P, _P, _P],
 }
 
 class SgdTensor(C.Structure):

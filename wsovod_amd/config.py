@@ -94,7 +94,8 @@ def _d2_defaults():
     _C.INPUT.RANDOM_FLIP = "horizontal"  # | "none" (detectron2's "vertical" is not built here)
     _C.INPUT.MIN_SIZE_TEST = 800
     _C.INPUT.MAX_SIZE_TEST = 1333
-    _C.INPUT.CROP = C({"ENABLED": False})
+    # detectron2's defaults; the training input stage builds the crop with MODEL.HIP.INPUT_CROP only
+    _C.INPUT.CROP = C({"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]})
     _C.DATASETS = C()
     _C.DATASETS.TRAIN = ()
     _C.DATASETS.TEST = ()
@@ -258,6 +259,9 @@ def add_wsovod_config(cfg):
     # training input stage (ResizeShortestEdge, RandomFlip, transform_proposals, zero padding) for the whole batch on the device
     # instead of PIL / numpy per image on the host (data/train_input.py).  Opt-in
     _C.MODEL.HIP.INPUT_DEVICE = False
+    # build T.RandomCrop (INPUT.CROP.ENABLED / TYPE / SIZE) in the training input stage, host and device route (DESIGN.md
+    # section 6e).  Off by default only because configs without the key are pinned to the earlier refusal of INPUT.CROP.ENABLED
+    _C.MODEL.HIP.INPUT_CROP = False
     return _C
 
 

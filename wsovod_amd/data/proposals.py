@@ -22,7 +22,7 @@ import torch
 from ..structures import Boxes, Instances
 
 __all__ = ["load_proposals_into_dataset", "unique_boxes", "transform_proposals", "load_class_embeddings",
-           "load_d2_pickle_into", "ResizeTransform", "HFlipTransform", "TransformList", "XYXY_ABS", "XYWH_ABS"]
+           "load_d2_pickle_into", "CropTransform", "ResizeTransform", "HFlipTransform", "TransformList", "XYXY_ABS", "XYWH_ABS"]
 
 XYXY_ABS, XYWH_ABS = 0, 1  # detectron2.structures.BoxMode values
 
@@ -72,6 +72,22 @@ def unique_boxes(boxes, scale=1.0):
     hashes = np.round(arr * scale).dot(v).astype(int)
     _, index = np.unique(hashes, return_index=True)
     return np.sort(index)
+
+
+class CropTransform:
+    """fvcore CropTransform: the image becomes img[y0:y0+h, x0:x0+w]; coordinates move by (-x0, -y0)."""
+
+    def __init__(self, x0, y0, w, h):
+        self.x0, self.y0, self.w, self.h = x0, y0, w, h
+
+    def apply_image(self, img):
+        return img[self.y0:self.y0 + self.h, self.x0:self.x0 + self.w]
+
+    def apply_coords(self, coords):
+        coords = coords.copy()
+        coords[:, 0] -= self.x0
+        coords[:, 1] -= self.y0
+        return coords
 
 
 class ResizeTransform:

@@ -1865,19 +1865,23 @@ def _table_pool(device):
     return pool
 
 
-def resample_u8_batch(images, sizes, flips, interleaved=False, out=None):
+def resample_u8_batch(images, sizes, flips, interleaved=False, out=None, windows=None):
     """The images of a training batch resized (PIL.Image.resize((nw, nh), BILINEAR), byte for byte), mirrored where flips[g]
     and zero-padded into one uint8 canvas (G, 3, max nh, max nw): two launches per INPUT_MAX_IMAGES images.
     images[g]: a contiguous uint8 device tensor, plane-major (3, H, W) or -- interleaved (one bool, or one per image) --
     (H, W, 3); sizes[g] = (nh, nw).  out: a contiguous uint8 (G, 3, max nh, max nw) device tensor to write instead of a new
-    one (every byte of it is written).  Raises `Unsupported` for what the kernel refuses."""
+    one (every byte of it is written).  windows: None, or per image (y0, x0, ch, cw) -- the resize reads
+    images[g][y0:y0+ch, x0:x0+cw] (CropTransform.apply_image) and nothing outside it -- or None for the whole image; with
+    windows the call goes through wsovod_resample_u8_batch_win.  Raises `Unsupported` for what the kernel refuses."""
     G = len(images)
     if G == 0 or len(sizes) != G or len(flips) != G:
         raise RuntimeError("resample_u8_batch: one size and one flip per image, at least one image")
     inter = [bool(interleaved)] * G if isinstance(interleaved, (bool, int)) else [bool(v) for v in interleaved]
     require_gpu(*images)
     dev = images[0].device
-    geo = []
+    if windows is not None and len(windows) != G:
+        raise RuntimeError("resample_u8_batch: one window (or None) per image")
+    geo, wins = [], []
     for g, (im, il) in enumerate(zip(images, inter)):
         if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2 if il else 0] != 3 or not im.is_contiguous() or im.numel() == 0:
             raise RuntimeError(f"resample_u8_batch: image {g}: a contiguous uint8 {'(H, W, 3)' if il else '(3, H, W)'} tensor "
@@ -1886,6 +1890,13 @@ def resample_u8_batch(images, sizes, flips, interleaved=False, out=None):
         nh, nw = int(sizes[g][0]), int(sizes[g][1])
         if nh <= 0 or nw <= 0:
             raise RuntimeError(f"resample_u8_batch: image {g}: empty size {nh} x {nw}")
+        if windows is not None:  # from here on (Hh, Ww) is the window's size; its place and strides go to `wins`
+            y0, x0, ch, cw = (0, 0, Hh, Ww) if windows[g] is None else (int(v) for v in windows[g])
+            if not (0 <= y0 and 0 <= x0 and ch > 0 and cw > 0 and y0 + ch <= Hh and x0 + cw <= Ww):
+                raise RuntimeError(f"resample_u8_batch: image {g}: window ({y0}, {x0}, {ch}, {cw}) outside {Hh} x {Ww}")
+            sc, sy, sx = (1, 3 * Ww, 3) if il else (Hh * Ww, Ww, 1)
+            wins.append((y0 * sy + x0 * sx, sc, sy, sx))
+            Hh, Ww = ch, cw
         geo.append((Hh, Ww, nh, nw))
     Hp, Wp = max(q[2] for q in geo), max(q[3] for q in geo)
     pool = _table_pool(dev)
@@ -1897,13 +1908,18 @@ def resample_u8_batch(images, sizes, flips, interleaved=False, out=None):
     slot = 3 * Hp * Wp
     for g0 in range(0, G, INPUT_MAX_IMAGES):  # (a multiple of 32 slots further the canvas is 4-byte aligned again)
         n = min(INPUT_MAX_IMAGES, G - g0)
-        batch = _lib.ResampleBatch()
+        batch = _lib.ResampleBatch() if windows is None else _lib.ResampleWindowBatch()
+        entry = lib().wsovod_resample_u8_batch if windows is None else lib().wsovod_resample_u8_batch_win
         batch.n = n
         at = 0
         for j in range(n):
             (Hh, Ww, nh, nw), d = geo[g0 + j], batch.img[j]
             d.src, d.H, d.W, d.nh, d.nw = images[g0 + j].data_ptr(), Hh, Ww, nh, nw
-            d.flags = (_lib.RESAMPLE_FLIP if flips[g0 + j] else 0) | (_lib.RESAMPLE_INTERLEAVED if inter[g0 + j] else 0)
+            if windows is None:
+                d.flags = (_lib.RESAMPLE_FLIP if flips[g0 + j] else 0) | (_lib.RESAMPLE_INTERLEAVED if inter[g0 + j] else 0)
+            else:
+                off, d.stride_c, d.stride_y, d.stride_x = wins[g0 + j]
+                d.src, d.src_bytes, d.flip = d.src + off, images[g0 + j].numel() - off, 1 if flips[g0 + j] else 0
             if Ww != nw:
                 d.kk_h, d.bounds_h, d.ksize_h = where[(Ww, nw)]
                 d.tmp = at
@@ -1911,25 +1927,26 @@ def resample_u8_batch(images, sizes, flips, interleaved=False, out=None):
             if Hh != nh:
                 d.kk_v, d.bounds_v, d.ksize_v = where[(Hh, nh)]
         scratch = torch.empty((at,), dtype=torch.uint8, device=dev) if at else None
-        _check_unsupported(lib().wsovod_resample_u8_batch(C.byref(batch), ptr(tables), tables.numel(), ptr(scratch), at,
-                                                          C.c_void_p(canvas.data_ptr() + g0 * slot), Hp, Wp, stream()),
-                           "resample_u8_batch")
+        _check_unsupported(entry(C.byref(batch), ptr(tables), tables.numel(), ptr(scratch), at,
+                                 C.c_void_p(canvas.data_ptr() + g0 * slot), Hp, Wp, stream()), "resample_u8_batch")
     return canvas
 
 
-def transform_proposals(boxes, logits, segments, topk):
+def transform_proposals(boxes, logits, segments, topk, crops=None):
     """data/proposals.py:transform_proposals for every image of a batch on the device, bit for bit.  boxes (N, 4) float32
     XYXY_ABS and logits (N,) float32 hold the images' rows back to back; segments[g] = (start, count, h, w, new_h, new_w,
-    flip).  Returns (out_boxes (G, topk, 4), out_logits (G, topk), counts (G,) int32): image g's survivors are
-    out_boxes[g, :counts[g]], the rows behind them zero.  Raises `Unsupported` for what the kernel refuses."""
+    flip).  crops: None, or per image (x0, y0) -- CropTransform in front of the list; (h, w) of the segment is then the
+    crop's size -- or None for no crop; with crops the call goes through wsovod_transform_proposals_win.  Returns
+    (out_boxes (G, topk, 4), out_logits (G, topk), counts (G,) int32): image g's survivors are out_boxes[g, :counts[g]], the
+    rows behind them zero.  Raises `Unsupported` for what the kernel refuses."""
     require_gpu(boxes, logits)
     if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 4 or logits.dtype != torch.float32 \
             or logits.dim() != 1 or logits.shape[0] != boxes.shape[0]:
         raise RuntimeError(f"transform_proposals: float32 (N, 4) boxes and (N,) logits expected, got {boxes.dtype} "
                            f"{tuple(boxes.shape)} / {logits.dtype} {tuple(logits.shape)}")
     G, N, topk, dev = len(segments), int(boxes.shape[0]), int(topk), boxes.device
-    if G == 0 or topk < 1:
-        raise RuntimeError("transform_proposals: at least one image and topk >= 1")
+    if G == 0 or topk < 1 or (crops is not None and len(crops) != G):
+        raise RuntimeError("transform_proposals: at least one image, topk >= 1 and one crop (or None) per image")
     boxes, logits = boxes.contiguous(), logits.contiguous()
     f32 = lambda v: C.c_float(v).value  # noqa: E731 -- the double rounded to float32, as numpy rounds a Python scalar
     out_boxes = torch.empty((G, topk, 4), dtype=torch.float32, device=dev)
@@ -1939,14 +1956,16 @@ def transform_proposals(boxes, logits, segments, topk):
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     for g0 in range(0, G, INPUT_MAX_IMAGES):
         n = min(INPUT_MAX_IMAGES, G - g0)
-        batch = _lib.ProposalBatch()
+        batch = _lib.ProposalBatch() if crops is None else _lib.ProposalWindowBatch()
+        entry = lib().wsovod_transform_proposals if crops is None else lib().wsovod_transform_proposals_win
         batch.n = n
         for j in range(n):
             start, count, h, w, nh, nw, flip = segments[g0 + j]
             d = batch.img[j]
             d.start, d.count, d.sx, d.sy = int(start), int(count), f32(nw * 1.0 / w), f32(nh * 1.0 / h)
             d.flip, d.flip_w, d.clip_w, d.clip_h = 1 if flip else 0, f32(nw), f32(nw), f32(nh)
-        _check_unsupported(lib().wsovod_transform_proposals(
-            C.byref(batch), ptr(boxes), ptr(logits), N, topk, ptr(ws), ws_bytes, ptr(out_boxes[g0]), ptr(out_logits[g0]),
-            ptr(counts[g0:]), stream()), "transform_proposals")
+            if crops is not None and crops[g0 + j] is not None:
+                d.has_crop, d.crop_x, d.crop_y = 1, f32(crops[g0 + j][0]), f32(crops[g0 + j][1])
+        _check_unsupported(entry(C.byref(batch), ptr(boxes), ptr(logits), N, topk, ptr(ws), ws_bytes, ptr(out_boxes[g0]),
+                                 ptr(out_logits[g0]), ptr(counts[g0:]), stream()), "transform_proposals")
     return out_boxes, out_logits, counts

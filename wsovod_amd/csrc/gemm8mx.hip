@@ -360,6 +360,9 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
     MX_OPT_IN(false, 0); MX_OPT_IN(false, 1); MX_OPT_IN(false, 4);
     MX_OPT_IN(true, 0); MX_OPT_IN(true, 1); MX_OPT_IN(true, 2); MX_OPT_IN(true, 3);
 #undef MX_OPT_IN
+#define MX_OPT_IN_T(E) WS_OPT_IN_LDS((gemm256_mx_kernel<true, E, true>), lds_bytes, "wsovod_gemm_f16mx: LDS opt-in")
+    MX_OPT_IN_T(0); MX_OPT_IN_T(1); MX_OPT_IN_T(2); MX_OPT_IN_T(3);
+#undef MX_OPT_IN_T
     WS_OPT_IN_LDS((gemm256_mx_br_kernel<true, 0>), lds_bytes, "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
     WS_OPT_IN_LDS((gemm256_mx_br_kernel<true, 1>), lds_bytes, "wsovod_gemm_f16mx_conv_branches: LDS opt-in");
 #define MX_OPT_IN_X(E) WS_OPT_IN_LDS((gemm256_mx_brx_kernel<true, E>), lds_bytes, "wsovod_gemm_f16mx_conv_branches_ex: LDS opt-in")
@@ -375,7 +378,10 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
   // again (res5: 84 tiles x 3 = 252).  Measured (tools/mx_conv_ab.py, 32 images): res5 1.833 -> 1.780 ms per conv; a last
   // round that is more than half full (res4: 170 tiles) is left alone -- its slices' workspace traffic and shorter K loops cost
   // more than the idle CUs, which the chip gives back as clock under its power limit (0.509 -> 0.560 ms with 170 x 3).
-  const int n_cu = wsovod::cu_count();
+  int n_cu = wsovod::cu_count();
+  // (WSOVOD_MX_TAIL_CUS=n: the round arithmetic below as on a chip of n CUs -- tests reach the K-slices at a few tiles)
+  if (const char* e = getenv("WSOVOD_MX_TAIL_CUS"))
+    if (atoi(e) > 0) n_cu = atoi(e);
   const int ntiles = a.tiles_m * a.tiles_n, nk_all = a.K / 64;
   int tail_mt = 0, S = 1;
   {
@@ -459,7 +465,17 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
                     : (d->dtype_c == WSOVOD_F32 && mxr && d->conv) ? 3
                     : (d->dtype_c == WSOVOD_BF16X2 && !d->residual && !d->conv) ? 4 : 0;
 #define MX_LAUNCH(C, E) hipLaunchKernelGGL((gemm256_mx_kernel<C, E>), dim3(grid), dim3(512), lds_bytes, s, qq)
-    if (d->conv) {
+#define MX_LAUNCH_T(E) hipLaunchKernelGGL((gemm256_mx_kernel<true, E, true>), dim3(grid), dim3(512), lds_bytes, s, qq)
+    // the conv's tap state as running offsets (the kernel's TAPTAB) unless WSOVOD_MX_TAPTAB=0 (the (r, q, c0) form: A/B runs,
+    // tests/test_gpu_mx_conv_taptable.py; kept for one release) or a border tap's offset | 2^31 + its scalar offset could
+    // reach 2^32 (maps next to the 2 GiB limit)
+    const long long span = qq.g.a_bytes + 2ll * ((long long)(qq.g.KH - 1) * qq.g.dil * qq.g.W + (long long)(qq.g.KW - 1) * qq.g.dil + 1) * qq.g.Cin * 2 + 128;
+    if (d->conv && !wsovod::env_off("WSOVOD_MX_TAPTAB") && span < (1ll << 31)) {
+      if (epi == 1) MX_LAUNCH_T(1);
+      else if (epi == 2) MX_LAUNCH_T(2);
+      else if (epi == 3) MX_LAUNCH_T(3);
+      else MX_LAUNCH_T(0);
+    } else if (d->conv) {
       if (epi == 1) MX_LAUNCH(true, 1);
       else if (epi == 2) MX_LAUNCH(true, 2);
       else if (epi == 3) MX_LAUNCH(true, 3);
@@ -470,6 +486,7 @@ static int gemm_f16mx_impl(const wsovod_gemm_desc* d, const unsigned char* a_sca
       else MX_LAUNCH(false, 0);
     }
 #undef MX_LAUNCH
+#undef MX_LAUNCH_T
   };
   if (tail_mt == 0) {
     launch(q, ntiles);

@@ -7,12 +7,16 @@
 // of code behind runtime branches that each tile streamed through the instruction cache; the hot combinations are built
 // apart): 1 = f16mx out, no residual; 2 = f16mx out + f16mx residual; 3 = fp32 out + f16mx residual; 4 = bf16x2 out, no
 // residual -- each with N a multiple of 64 (the staged row-image stores).
+// TAPTAB (conv form): the state of the K-step requested next as running scalar offsets + a per-lane shift of the tap
+// validity bits (below) instead of the (r, q, c0) tap state and its per-K-step multiplications and compares.  The same
+// addresses, so the same bits; the branch-batched forms and WSOVOD_MX_TAPTAB=0 keep the (r, q, c0) form.
 #if !defined(WSOVOD_CONV_BRANCHES)
-template <bool CONV, int EPI = 0>
+template <bool CONV, int EPI = 0, bool TAPTAB = false>
 __global__ __launch_bounds__(512) void gemm256_mx_kernel(const MxArgs q) {
+  static_assert(CONV || !TAPTAB, "the tap state belongs to the conv form");
   const GemmArgs& p = q.g;
 #else  // the branch-batched conv forms (MxBrArgs / MxBrExArgs): the same text, compiled again under another name
-template <bool CONV, int EPI = 0>
+template <bool CONV, int EPI = 0, bool TAPTAB = false>
 #if defined(WSOVOD_CONV_BRANCHES_EX)
 __global__ __launch_bounds__(512) void gemm256_mx_brx_kernel(const MxBrExArgs q) {
 #else
@@ -137,6 +141,44 @@ __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
       va[i] = (vmask[i] & tapbit) ? pixb[i] : alt;
     }
   };
+  // TAPTAB: the request stream's state as it runs -- `left` main K-steps remain (<= 0: the fused shortcut's region), the
+  // tap's bit of a row's mask ends up in bit 31 after a left shift by sh = 31 - tap, soa / sob are the scalar offsets of
+  // soff_a / soff_b kept by increments (the K order is chunk-outer, tap-inner: + one filter column, + one filter row back to
+  // column 0, + one channel chunk back to tap 0, and 64 slots per K-step of the shortcut's region)
+  struct Req { int sh, q, left, soa, sob; };
+  [[maybe_unused]] Req rq{31, 0, 0, 0, 0};
+  [[maybe_unused]] unsigned nvm[4];  // (TAPTAB) bit t set: tap t of the row lies outside the image (or the row beyond M)
+  [[maybe_unused]] const int tt_taps = p.KH * p.KW;
+  [[maybe_unused]] const int tt_aq = p.dil * p.Cin * esz, tt_arow = (p.W - (p.KW - 1)) * tt_aq;
+  [[maybe_unused]] const int tt_achunk = BKE * esz - ((p.KH - 1) * p.W + (p.KW - 1)) * tt_aq, tt_aenter = tt_achunk - p.Cin * esz;
+  [[maybe_unused]] const int tt_btap = p.Cin * esz, tt_bchunk = BKE * esz - (tt_taps - 1) * tt_btap;
+  [[maybe_unused]] auto req_next = [&](const Req s) {
+    // (the increments read into values FIRST: from `c ? x : y` on the captured constants hipcc built a table of their
+    // addresses in scratch and loaded through it)
+    const int aq = tt_aq, arow = tt_arow, achunk = tt_achunk, aenter = tt_aenter, btap = tt_btap, bchunk = tt_bchunk;
+    const int last_sh = 32 - tt_taps, kw = p.KW;
+    const bool sec = s.left <= 0, sec1 = s.left <= 1;  // this K-step / the next one in the shortcut's region
+    const int q1 = s.q + 1;
+    const bool wq = q1 >= kw, wt = s.sh <= last_sh;  // last filter column / last tap of the chunk
+    const int da_main = wt ? achunk : (wq ? arow : aq), da_sec = sec ? BKE * esz : aenter, db_main = wt ? bchunk : btap;
+    Req n;
+    n.q = wq ? 0 : q1;
+    n.sh = wt ? 31 : s.sh - 1;
+    n.left = s.left - 1;
+    n.soa = s.soa + (sec1 ? da_sec : da_main);
+    n.sob = s.sob + (sec1 ? BKE * esz : db_main);
+    return n;
+  };
+  // per-lane offsets for the K-step of state s: pixb with bit 31 set where the tap is invalid (pixb < 2^31, and the launcher
+  // keeps pixb + soa below 2^31 too: the sum stays out of range without wrapping), the shortcut's pixel in its region
+  [[maybe_unused]] auto conv_va_tt = [&](const Req s) {
+    const unsigned secm = s.left <= 0 ? 0xffffffffu : 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned main_v = ((nvm[i] << s.sh) & OOB) | pixb[i];
+      va[i] = (pix2v[i] & secm) | (main_v & ~secm);
+    }
+  };
   // scalar byte offsets of a K-step: into the A operand (conv: the tap's displacement + channel chunk) and the B rows
   auto soff_a = [&](int kt, const Tap t) -> int {
     if (!CONV) return (kt + kt_base) * (BKE * esz);
@@ -202,8 +244,22 @@ __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
       unsigned mk = 0;
       for (int r = 0; r < p.KH; ++r) mk |= ((rowm >> r) & 1u) ? (colm << (r * p.KW)) : 0u;
       vmask[i] = mk;
+      nvm[i] = ~mk;
     }
   }
+  if constexpr (CONV && TAPTAB) {
+    rq = Req{31 - (t2.r * p.KW + t2.q), t2.q, tt_taps * (p.Cin / BKE) - kt_base, soff_a(0, t2), soff_b(0, t2)};
+    constexpr int ST = BM * 128;
+    conv_va_tt(rq);
+    dma_a(0, 0, rq.soa, rq.left <= 0); dma_a(0, 2, rq.soa, rq.left <= 0); dma_a(0, 1, rq.soa, rq.left <= 0); dma_a(0, 3, rq.soa, rq.left <= 0);
+    rq = req_next(rq);
+    if (nk > 1) {
+      conv_va_tt(rq);
+      dma_a(ST, 0, rq.soa, rq.left <= 0); dma_a(ST, 2, rq.soa, rq.left <= 0); dma_a(ST, 1, rq.soa, rq.left <= 0); dma_a(ST, 3, rq.soa, rq.left <= 0);
+    }
+    rq = req_next(rq);
+    conv_va_tt(rq);
+  } else {
   {
     if constexpr (CONV) conv_va(t2);
     const int sa0 = soff_a(0, t2);
@@ -221,6 +277,7 @@ __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
   if constexpr (CONV) {
     t2 = tap_next(t2);
     conv_va(t2);
+  }
   }
 
   // ---- block scales: per lane the rows of its 4 A tiles and 2 B tiles; loop constants inside a row segment.  The ql lanes
@@ -343,8 +400,8 @@ __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
     const unsigned a0 = cA0 + (unsigned)offA, a1 = cA1 + (unsigned)offA, a2 = cA2 + (unsigned)offA, a3 = cA3 + (unsigned)offA;
     const unsigned b0 = cB0 + (unsigned)offB, b1 = cB1 + (unsigned)offB, b2 = cB2 + (unsigned)offB, b3 = cB3 + (unsigned)offB;
     const bool more2 = kt + 2 < nk;
-    const int soa = soff_a(kt + 2, t2), sob = soff_b(kt + 2, t2);  // (scalar)
-    const bool sec2 = CONV && t2.c0 >= p.Cin;
+    const int soa = TAPTAB ? rq.soa : soff_a(kt + 2, t2), sob = TAPTAB ? rq.sob : soff_b(kt + 2, t2);  // (scalar)
+    const bool sec2 = CONV && (TAPTAB ? rq.left <= 0 : t2.c0 >= p.Cin);
     // ---- phase A: A rows 0-63 (tiles 0, 1) x all 64 columns (tiles 0, 1) of this wavefront: 16 fragment reads
     MX_STAMP0();
 #if !defined(MX_ABL_NOREAD)
@@ -393,8 +450,14 @@ __global__ __launch_bounds__(512) void gemm256_mx_br_kernel(const MxBrArgs q) {
         // section behind the DMA issue: interleaved with the products of this phase (gemm8.hip's place for them) they made
         // the 512-cycle product block of this format ~100 cycles longer (tools/mx_conv_ab.py: 7.80 -> 7.59 ms for the eight
         // convs); the empty asm keeps hipcc from sinking the selects to their use in front of the next K-step's DMA issue
-        t2 = tap_next(t2);
-        conv_va(t2);
+        // (TAPTAB: 12 VALU + 17 scalar, no multiplication, nothing of it at the top of the K-step)
+        if constexpr (TAPTAB) {
+          rq = req_next(rq);
+          conv_va_tt(rq);
+        } else {
+          t2 = tap_next(t2);
+          conv_va(t2);
+        }
         asm volatile("" : "+v"(va[0]), "+v"(va[1]), "+v"(va[2]), "+v"(va[3]));
       }
       MX_VMCNT(8);  // younger: the eight pieces of K-step kt + 2 -> K-step kt + 1 has landed
